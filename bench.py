@@ -17,8 +17,12 @@ and classifies its partition, and -rc adds an all-reduce of the per-name sums
 (frender_amd/dist.py; --merge tree sends everything to rank 0 instead).
 
 Prints ONE JSON line (rank 0): value = total reads of all ranks / max-over-ranks
-step time, plus roofline (tally kernel, HIP events on the library's stream) and
-cpu_baseline (the oracle's CPU port timed on a bounded sample on this host).
+step time, plus roofline (tally kernel, HIP events on the library's stream in the
+last timed step).  A plain run does only that: set up, warm up, time --steps
+steps, write --dump-outputs, print.  --full adds, after the timed steps and at
+N=1, the reference-pin check of the benchmarked table (config.reference_pin),
+cpu_baseline (the oracle's CPU port timed on a bounded sample on this host) and
+e2e (the product `scan` command on the same .fastq.gz files).
 """
 from __future__ import annotations
 
@@ -39,6 +43,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need (N=1): the "
+                         "reference-pin check of the benchmarked table, cpu_baseline and e2e (each still has its "
+                         "own --no-pin / --no-cpu / --no-single)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (the table in its order "
+                         "and every code's classification) as DIR/<name>.npy, float64 / float32, under 64 MB "
+                         "(N=1, not with --merge-leg; see dump_outputs)")
     ap.add_argument("--reads", type=int, default=100_000_000, help="reads per GPU")
     ap.add_argument("--samples", type=int, default=96)
     ap.add_argument("--index-len", type=int, default=8)
@@ -468,6 +480,45 @@ def pin_check(args, ctx, sheet):
                       f"the same records (imported in the build container by {pin.get('generated_by', '').split(':')[0]})"}
 
 
+DUMP_ROWS = 1_000_000  # --dump-outputs: table rows written (56 B per row in all files: under 64 MB)
+
+
+def dump_outputs(args, ctx, U, csum, outdir, rc_sums=None):
+    """--dump-outputs DIR: what the last timed step left in the context for its caller, as float64 /
+    float32 .npy files (every value is an integer that the format holds exactly):
+      table.npy    f64 [4]     unique codes, reads (sum of the counts), table_checksum's low and high 32 bits
+      rows.npy     f64 [k]     the table rows written: all U in the table's order, or, above DUMP_ROWS rows, a
+                               fixed sample of DUMP_ROWS of them (numpy default_rng(0), ascending)
+      keys.npy     f64 [k, 2]  each row's packed code, low and high 32 bits (a key has up to 63 bits)
+      counts.npy   f64 [k]     its reads
+      first.npy    f64 [k]     the ordinal of its first record
+      classes.npy  f32 [k, 4]  fr_classify's m1, m2, cls, row of the step's last pass (with --rc pass B)
+      rc_counts.npy f64 [2, names]  with --rc: pass A's per-name reads with the forward / the rc idx2
+    The table is the step's own.  The classification stays in HBM in the timed step (to_host=False), so
+    it is fetched by running that step's last classify call again on the same table and sheet, with host
+    arrays.  rc_sums: the (forward, rc) sums that the step read after its pass A (every fr_classify call
+    zeroes the library's sums and only an rc pass adds to them, so after pass B they are gone from the
+    context).  Inputs are SYN-v1 records (seed 1), so the same arguments give the same files."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    keys, counts, first = ctx.unique()
+    assert keys.size == U, (keys.size, U)
+    out = {"table": np.array([U, int(counts.sum()), csum & 0xFFFFFFFF, csum >> 32], dtype=np.float64)}
+    if args.rc:
+        out["rc_counts"] = np.stack([np.asarray(x, dtype=np.float64) for x in rc_sums])
+    cl = ctx.classify(args.nsubs, False)
+    rows = np.arange(U) if U <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(U, DUMP_ROWS, replace=False))
+    out["rows"] = rows.astype(np.float64)
+    k = keys[rows]
+    out["keys"] = np.stack([k & np.uint64(0xFFFFFFFF), k >> np.uint64(32)], axis=1).astype(np.float64)
+    out["counts"] = counts[rows].astype(np.float64)
+    out["first"] = first[rows].astype(np.float64)
+    out["classes"] = np.stack([cl[c][rows] for c in ("m1", "m2", "cls", "row")], axis=1).astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def rank_check(world):
     """--rank-check: the launcher's ranks meet over gloo; rank 0 prints the world size they agree on."""
     import torch
@@ -484,6 +535,16 @@ def rank_check(world):
 
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be at least 1 and --warmup at least 0", file=sys.stderr)
+        return 2
+    if args.dump_outputs and args.gpus != 1:
+        print("bench.py: --dump-outputs writes one GPU's table: run it with --gpus 1", file=sys.stderr)
+        return 2
+    if args.dump_outputs and args.merge_leg:
+        print("bench.py: --dump-outputs writes the last timed step's outputs, and --merge-leg runs three more "
+              "steps after the timed ones: run them separately", file=sys.stderr)
+        return 2
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # `bench.py --gpus N` without a launcher: one child rank per GPU, before anything touches a GPU
@@ -553,6 +614,7 @@ def main():
     cuts = [(n * i // max(args.files, 1)) // 8 * 8 for i in range(max(args.files, 1))] + [n]
     tally_timing = []
     timing_on = [False]  # the step whose tally launches are timed (the last timed one) reads them back
+    rc_sums = [None]  # --rc: the last step's per-name (forward, rc) sums, as read after its pass A
 
     def step():
         ctx.reset()
@@ -587,6 +649,7 @@ def main():
                 f, r = ctx.rc_counts()
                 if world > 1 and args.merge == "a2a":  # per-name sums over all partitions
                     f, r = reduce_sum(dist, wire, list(f)), reduce_sum(dist, wire, list(r))
+                rc_sums[0] = (f, r)  # pass B's classify zeroes them in the context: kept for --dump-outputs
                 use = [int(a) < int(b) for a, b in zip(f, r)]
                 # pass B's idx2 and its reverse complements are selections (rc(rc(x)) = x)
                 if any(use):
@@ -675,12 +738,14 @@ def main():
     if world > 1 and args.merge == "a2a":  # report the merged table's size (sum of the partitions)
         U, csum = (int(x) for x in reduce_sum(dist, wire, [U, csum]))
     csum &= (1 << 64) - 1
+    if args.dump_outputs:
+        dump_outputs(args, ctx, int(U), csum, args.dump_outputs, rc_sums[0])
     pinned = None
     pp = pin_path(args)
-    if world == 1 and pp and os.path.exists(pp) and not args.no_pin:
+    if args.full and world == 1 and pp and os.path.exists(pp) and not args.no_pin:
         pinned = pin_check(args, ctx, sheet)
     if rank == 0:
-        cpu = None if (args.no_cpu or world > 1) else cpu_baseline(args, ctx, sheet, reclen)  # N=1 only
+        cpu = cpu_baseline(args, ctx, sheet, reclen) if args.full and world == 1 and not args.no_cpu else None
         value = world * n / (ms / 1e3) / 1e6
         out = {
             "metric": "M reads/sec scanned+classified (96 samples, 8+8bp, n=1) at 1/2/4/8 MI355X",

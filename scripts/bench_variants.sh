@@ -4,6 +4,8 @@
 #             "noins|--tuning log_min=0|noins" runs frender_amd/libfrender_hip_exp_noins.so: scripts/build_exp.sh)
 #   ROUNDS (default 2), STEPS (10), OUT (gpurun_out/variants.jsonl), TIMEOUT per run (240 s)
 # Every run: --no-cpu; a run that fails or times out ends the script (nothing more runs on the GPU).
+# The "pin" field (config.reference_pin.equal) is null for a plain run: give a variant --full in its arguments
+# to have its table checked against the reference's pin after the timed steps.
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"; mkdir -p gpurun_out
 OUT=${OUT:-gpurun_out/variants.jsonl}

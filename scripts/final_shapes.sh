@@ -14,8 +14,9 @@ run() {  # name, args
   timeout -k 10 400 python bench.py --steps 5 --warmup 2 --no-cpu $2 > gpurun_out/shapes/$1.log 2>&1 || { echo "$1 failed"; tail -3 gpurun_out/shapes/$1.log; exit 1; }
   grep "^{" gpurun_out/shapes/$1.log | tail -1 | cut -c1-200
 }
-run cfg3 "$CFG3"
-run cfg4 "--combinatorial --nsubs 2"
-run r150 "--read-len 150 --reads 20000000"
-run files8 "--files 8"
-run files1 ""
+# --full (with run's --no-cpu): the reference-pin check of the pinned shapes after the timed steps, as before
+run cfg3 "--full $CFG3"
+run cfg4 "--full --combinatorial --nsubs 2"
+run r150 "--full --read-len 150 --reads 20000000"
+run files8 "--full --files 8"
+run files1 "--full"

@@ -2,6 +2,8 @@
 # On-box check: GPU parity tests, a short bench, and a rocprofv3 kernel-trace of the bench.
 # Every GPU step has its own time limit; a crash/timeout ends the script.
 #   stage: all | test | bench | prof | dist
+#   BENCH_ARGS: more bench.py arguments for the bench and prof stages (the bench stage is a plain run;
+#               BENCH_ARGS=--full adds the reference-pin check, cpu_baseline and e2e to its line)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOT=$(pwd)
