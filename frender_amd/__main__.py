@@ -16,7 +16,7 @@ def _single_process():
         _runtime.USE_TORCH = False
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(prog="frender_amd")
     sub = parser.add_subparsers()
     p = sub.add_parser("scan", help="Scan file(s) or directory and compare to a supplied barcode table")
@@ -35,6 +35,10 @@ def main(argv=None):
                    help=".csv barcode association table; required unless a directory holding one is given")
     p.add_argument("--gpus", type=int, default=1,
                    help="GPUs (one process each; files are sharded over them, rank 0 writes the outputs)")
+    p.add_argument("--gz-reader", choices=("host", "gpu"), default="host",
+                   help="who inflates the inputs: host (default: the native thread pool) or gpu (BGZF files are "
+                        "inflated on the GPU, one member per wave; other files, and every file with -s, stay with "
+                        "the host pool; single GPU)")
     p.add_argument("files", nargs="+", help="Fastq file(s) or a directory of fastq files")
     p.set_defaults(cmd="scan")
     d = sub.add_parser("demux", help="Demultiplex paired fastq files using a frender scan result file")
@@ -65,8 +69,16 @@ def main(argv=None):
     d.add_argument("--stage-times", action="store_true", help="print the demux's seconds per stage (stderr)")
     d.add_argument("files", nargs="+", help="Fastq file, list of fastq files, or directory path")
     d.set_defaults(cmd="demux")
+    return parser
+
+
+def main(argv=None):
+    parser = build_parser()
     args = parser.parse_args(argv)
     if getattr(args, "cmd", None) == "scan":
+        if args.gz_reader == "gpu" and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+            parser.error("--gz-reader gpu is a single-GPU reader: run it without --gpus (multi-GPU scans inflate on "
+                         "the host)")
         if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
             return launch_ranks(args.gpus, sys.argv[1:] if argv is None else list(argv))
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:

@@ -163,6 +163,16 @@ _SIGS = {
     "fr_defl_out_bytes": (C.c_uint64, [P]),
     "fr_defl_stored_fallbacks": (C.c_uint64, [P]),
     "fr_defl_fetch": (C.c_int, [P, P, C.c_uint64]),
+    # GPU inflate (fr_inflate.hip)
+    "fr_infl_create": (P, [C.c_int]),
+    "fr_infl_destroy": (None, [P]),
+    "fr_infl_last_error": (C.c_char_p, [P]),
+    "fr_infl_run": (C.c_int, [P, P, P, P, P, C.c_int, P, P]),
+    "fr_infl_run_host": (C.c_int, [P, P, P, P, C.c_int, P, P]),
+    "fr_infl_fetch": (C.c_int, [P, P, C.c_uint64]),
+    "fr_infl_kernel_info": (C.c_int, [P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "fr_feed_bgzf": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_int), u64p, u64p]),
+    "fr_bgzf_probe": (C.c_int, [C.c_char_p, u64p, u64p]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _f = getattr(lib, _name)
@@ -561,6 +571,69 @@ class Deflater:
         return comp, crc, out
 
 
+class Inflater:
+    """GPU inflate of raw deflate streams of at most 64 KiB decoded each (fr_infl): see include/frender_amd.h."""
+
+    def __init__(self, device: int = 0):
+        self.h = lib.fr_infl_create(device)
+        err = lib.fr_infl_last_error(self.h) if self.h else b"fr_infl_create returned NULL"
+        if err:
+            raise FrenderError(f"fr_infl_create: {err.decode()}")
+
+    def close(self):
+        if self.h:
+            lib.fr_infl_destroy(self.h)
+            self.h = None
+
+    def _ck(self, rc, what):
+        if rc != FR_OK:
+            raise FrenderError(f"{what}: {lib.fr_infl_last_error(self.h).decode()} (rc={rc})")
+
+    def inflate(self, streams, in_off=None, out_off=None) -> tuple:
+        """Decode a list of (stream bytes, decoded size) pairs, packed back to back -- or the ranges
+        [in_off[s], in_off[s + 1]) of host bytes `streams` to out_off[s + 1] - out_off[s] bytes each:
+        (status per stream, CRC-32 per stream, the output buffer of out_off[-1] bytes)."""
+        if in_off is None:
+            data = b"".join(d for d, _ in streams)
+            in_off = np.concatenate([[0], np.cumsum([len(d) for d, _ in streams])])
+            out_off = np.concatenate([[0], np.cumsum([n for _, n in streams])])
+        else:
+            data = streams
+        a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+        io, oo = np.ascontiguousarray(in_off, dtype=np.uint64), np.ascontiguousarray(out_off, dtype=np.uint64)
+        n = io.size - 1
+        if n and oo[0] != 0:
+            raise ValueError("Inflater.inflate: out_off must start at 0 (the output buffer is fetched from its start)")
+        status, crc = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        self._ck(lib.fr_infl_run_host(self.h, _ptr(a), _ptr(io), _ptr(oo), n, _ptr(status), _ptr(crc)),
+                 "fr_infl_run_host")
+        out = np.empty(int(oo[-1]) if n else 0, np.uint8)
+        self._ck(lib.fr_infl_fetch(self.h, _ptr(out), out.size), "fr_infl_fetch")
+        return status, crc, out
+
+    def run_device(self, dev_in: int, in_off, dev_out: int, out_off) -> tuple:
+        """fr_infl_run over device buffers the caller owns: (status, CRC-32) per stream."""
+        io, oo = np.ascontiguousarray(in_off, dtype=np.uint64), np.ascontiguousarray(out_off, dtype=np.uint64)
+        n = io.size - 1
+        status, crc = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        self._ck(lib.fr_infl_run(self.h, P(dev_in), _ptr(io), P(dev_out), _ptr(oo), n, _ptr(status), _ptr(crc)),
+                 "fr_infl_run")
+        return status, crc
+
+    def kernel_info(self) -> dict:
+        """The kernel's registers per lane and LDS per workgroup, and the last run's kernel time (HIP events)."""
+        v, l, ms = C.c_int(), C.c_int(), C.c_double()
+        self._ck(lib.fr_infl_kernel_info(self.h, C.byref(v), C.byref(l), C.byref(ms)), "fr_infl_kernel_info")
+        return {"vgprs": v.value, "lds_bytes": l.value, "last_ms": ms.value}
+
+
+def bgzf_probe(path) -> tuple:
+    """fr_bgzf_probe (headers only, no GPU): (the GPU reader would try the file, members, decoded bytes)."""
+    m, b = C.c_uint64(), C.c_uint64()
+    ok = lib.fr_bgzf_probe(os.fsencode(str(path)), C.byref(m), C.byref(b))
+    return bool(ok), int(m.value), int(b.value)
+
+
 def gzip_frame(crc: int, isize: int) -> tuple:
     """The header and trailer that make a raw deflate stream a gzip member (RFC 1952; XFL 2 and OS 255
     as Python's gzip writes them at level 9, mtime 0)."""
@@ -712,6 +785,13 @@ class Context:
         base = part.feed(self.h, file_index, lines_before)
         part.base = base
         return base
+
+    def feed_bgzf(self, path) -> tuple:
+        """The current file decoded on the GPU (fr_feed_bgzf): (decoded, members, bytes).  decoded False:
+        nothing was fed; the caller feeds the file through a GzPool."""
+        d, m, b = C.c_int(), C.c_uint64(), C.c_uint64()
+        self._ck(lib.fr_feed_bgzf(self.h, os.fsencode(str(path)), C.byref(d), C.byref(m), C.byref(b)), "fr_feed_bgzf")
+        return bool(d.value), int(m.value), int(b.value)
 
     def feed_device(self, dev_ptr: int, nbytes: int):
         self._ck(lib.fr_feed_device(self.h, P(dev_ptr), nbytes), "fr_feed_device")

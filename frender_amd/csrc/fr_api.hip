@@ -228,7 +228,14 @@ struct fr_ctx {
     double classify_ms = 0, finalize_ms = 0;
     bool timing = true;  // fr_set_timing: record the timing events
     bool fin_timed = false;  // the pending fr_finalize recorded fin_e0
+
+    fr_infl* infl = nullptr;  // fr_feed_bgzf's inflater (created at its first use; its buffers serve every file)
 };
+
+namespace fr {
+int infl_bgzf_file(fr_infl* z, const char* path, int* ok, const uint8_t** dev_out, uint64_t* out_len,
+                   uint64_t* members);  // fr_inflate.hip
+}
 
 #define CK(x)                                                                                  \
     do {                                                                                       \
@@ -771,6 +778,7 @@ fr_ctx* fr_create_tuned(int device, uint64_t chunk_bytes, uint64_t table_slots, 
 
 void fr_destroy(fr_ctx* ctx) {
     if (!ctx) return;
+    if (ctx->infl) fr_infl_destroy(ctx->infl);
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->copy) (void)hipStreamSynchronize(ctx->copy);
@@ -1213,6 +1221,40 @@ int fr_feed_device(fr_ctx* ctx, const uint8_t* dev_data, uint64_t len) {
     if (rc) return rc;
     if (len) ctx->last_byte = *ctx->h_byte;  // landed: read_state synchronised after the copy
     ctx->carry.clear();
+    return FR_OK;
+}
+
+int fr_feed_bgzf(fr_ctx* ctx, const char* path, int* decoded, uint64_t* members, uint64_t* bytes) {
+    if (!decoded || !path) return fail(ctx, FR_ERR_INVALID, "fr_feed_bgzf: null argument");
+    *decoded = 0;
+    if (members) *members = 0;
+    if (bytes) *bytes = 0;
+    if (!ctx->file_open) return fail(ctx, FR_ERR_INVALID, "fr_feed_bgzf: no open file");
+    if (ctx->file_base != 0 || ctx->file_offset != 0 || !ctx->carry.empty())
+        return fail(ctx, FR_ERR_INVALID, "fr_feed_bgzf takes a whole file from its first byte (no prior feed)");
+    if (ctx->max_records > 0) return FR_OK;  // -s: the host pool stops inflating at the sample's end
+    if (!ctx->infl) {
+        ctx->infl = fr_infl_create(ctx->device);
+        if (!ctx->infl || *fr_infl_last_error(ctx->infl)) {
+            const std::string msg = ctx->infl ? fr_infl_last_error(ctx->infl) : "fr_infl_create returned NULL";
+            if (ctx->infl) fr_infl_destroy(ctx->infl);
+            ctx->infl = nullptr;
+            return fail(ctx, FR_ERR_HIP, msg);
+        }
+    }
+    // status and CRC of every member are back on the host and checked against the trailers before
+    // anything reaches the tally: a declined file leaves nothing behind
+    int ok = 0;
+    const uint8_t* dev = nullptr;
+    uint64_t len = 0, n = 0;
+    int rc = infl_bgzf_file(ctx->infl, path, &ok, &dev, &len, &n);
+    if (rc) return fail(ctx, rc, std::string("fr_feed_bgzf: ") + fr_infl_last_error(ctx->infl));
+    if (!ok) return FR_OK;
+    rc = fr_feed_device(ctx, dev, len);
+    if (rc) return rc;
+    *decoded = 1;
+    if (members) *members = n;
+    if (bytes) *bytes = len;
     return FR_OK;
 }
 

@@ -34,6 +34,7 @@
 
 #include "../../include/frender_amd.h"
 #include "fr_deflate_core.h"
+#include "fr_internal.h"
 
 namespace {
 
@@ -463,6 +464,10 @@ uint32_t crc_apply(const uint32_t* T, uint32_t c) {
 }
 
 }  // namespace
+
+namespace fr {
+void crc_shift_table(uint64_t n, uint32_t* T) { ::crc_shift_table(n, T); }  // shared with fr_inflate.hip
+}
 
 struct fr_defl {
     int device = 0;

@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "../../include/frender_amd.h"
+#include "fr_internal.h"
 #include "fr_pinflate.h"
 
 // Byte buffers whose resize() does not zero-fill: every byte of a decode buffer is written by the
@@ -193,7 +194,7 @@ const Libdeflate* libdeflate() {
 
 constexpr size_t LD_MAX_IN = 256ull << 20;   // compressed bytes a file may have for the fast path
 constexpr size_t LD_MAX_OUT = 1ull << 30;    // decoded bytes it may produce
-constexpr size_t BGZF_MAX_IN = 1ull << 30;   // BGZF files: compressed bytes for the parallel path
+constexpr size_t BGZF_MAX_IN = fr::BGZF_MAX_IN;  // BGZF files: compressed bytes for the parallel path
 constexpr size_t BGZF_MAX_BLOCK = 65536;     // the format's bound on a member's size and ISIZE
 constexpr size_t BGZF_WINDOW = 64ull << 20;  // decoded bytes per parallel BGZF window
 constexpr size_t WHOLE_BUDGET = 6ull << 30;  // whole-file buffers (input + output) held at once per pool
@@ -212,10 +213,11 @@ inline uint32_t le32(const uint8_t* p) { return le16(p) | (le16(p + 2) << 16); }
 // and its decoded length in the trailer, so the members of one file are found by walking headers
 // alone and decode independently.  True with the member list when the whole file is such members
 // (NUL padding at the end allowed); anything else is not BGZF.
-bool bgzf_members(const Bytes& in, std::vector<Member>& ms) {
-    const size_t n = in.size();
+// *plain (optional): every member's FLG is FEXTRA alone (what the GPU reader takes, fr_feed_bgzf).
+bool bgzf_members(const uint8_t* in, size_t n, std::vector<Member>& ms, bool* plain = nullptr) {
     size_t pos = 0, dst = 0;
     ms.clear();
+    if (plain) *plain = true;
     while (pos < n) {
         if (in[pos] == 0) {  // trailing NUL padding only
             while (pos < n && in[pos] == 0) ++pos;
@@ -224,6 +226,7 @@ bool bgzf_members(const Bytes& in, std::vector<Member>& ms) {
         }
         if (n - pos < 18 || in[pos] != 0x1f || in[pos + 1] != 0x8b || in[pos + 2] != 8 || !(in[pos + 3] & 4))
             return false;
+        if (plain && in[pos + 3] != 4) *plain = false;
         const size_t xlen = le16(&in[pos + 10]);
         if (n - pos < 12 + xlen) return false;
         size_t bsize = 0;
@@ -407,7 +410,7 @@ bool inflate_whole(fr_gz* g, GzFile& f) {
     fclose(fp);
     if (got != n) return false;
     std::vector<Member> ms;
-    if (bgzf_members(in, ms)) {  // member-parallel, one window of about BGZF_WINDOW output bytes at a time
+    if (bgzf_members(in.data(), in.size(), ms)) {  // member-parallel, one window of about BGZF_WINDOW output bytes at a time
         size_t k0 = 0;
         while (k0 < ms.size()) {
             size_t k1 = k0;
@@ -998,8 +1001,9 @@ namespace {
 
 // the member table of a BGZF file from its headers and trailers alone; false when the file is not
 // wholly BGZF members (NUL padding at the end allowed) or cannot be read
-bool bgzf_table(FILE* fp, uint64_t csize, std::vector<Member>& ms) {
+bool bgzf_table(FILE* fp, uint64_t csize, std::vector<Member>& ms, bool* plain = nullptr) {
     ms.clear();
+    if (plain) *plain = true;
     uint64_t pos = 0, dst = 0;
     uint8_t h[18];
     while (pos < csize) {
@@ -1015,6 +1019,7 @@ bool bgzf_table(FILE* fp, uint64_t csize, std::vector<Member>& ms) {
         if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4) || le16(h + 10) != 6 || h[12] != 'B' ||
             h[13] != 'C' || le16(h + 14) != 2)
             return false;
+        if (plain && h[3] != 4) *plain = false;
         const uint64_t bsize = le16(h + 16) + 1u;
         uint8_t t[4];
         if (bsize < 26 || pos + bsize > csize || fseek(fp, (long)(pos + bsize - 4), SEEK_SET) != 0 ||
@@ -1323,3 +1328,44 @@ void fr_gz_close(fr_gz* g) {
 }
 
 }  // extern "C"
+
+// ---- the member table for the GPU reader (fr_feed_bgzf, fr_inflate.hip) -----------------------
+// The same walks as above, with what the GPU reader asks on top: in every member FLG == FEXTRA alone and
+// an extra field that is the BC subfield alone (XLEN 6, as bgzip and htslib write it), and the host path's
+// compressed-size budget.  fr_bgzf_probe (headers only) and bgzf_member_table (the file in memory) accept
+// the same files.
+
+namespace fr {
+
+bool bgzf_member_table(const uint8_t* data, size_t n, std::vector<BgzfMember>& out) {
+    std::vector<Member> ms;
+    bool plain = false;
+    out.clear();
+    if (n > BGZF_MAX_IN || !bgzf_members(data, n, ms, &plain) || !plain) return false;
+    out.reserve(ms.size());
+    for (const Member& m : ms) {
+        if (le16(data + m.off + 10) != 6) return false;  // bgzf_table's rule: what the probe says, the feed does
+        const size_t head = 12 + le16(data + m.off + 10);  // the deflate stream: after the extra field, before the trailer
+        out.push_back(BgzfMember{m.off + head, m.len - head - 8, m.dst, (uint32_t)m.isize, le32(data + m.off + m.len - 8)});
+    }
+    return true;
+}
+
+}  // namespace fr
+
+extern "C" int fr_bgzf_probe(const char* path, uint64_t* members, uint64_t* decoded_bytes) {
+    if (members) *members = 0;
+    if (decoded_bytes) *decoded_bytes = 0;
+    FILE* fp = path ? fopen(path, "rb") : nullptr;
+    if (!fp) return 0;
+    struct stat sb;
+    std::vector<Member> ms;
+    bool plain = false;
+    const bool ok = fstat(fileno(fp), &sb) == 0 && (size_t)sb.st_size <= BGZF_MAX_IN &&
+                    bgzf_table(fp, (uint64_t)sb.st_size, ms, &plain) && plain;
+    fclose(fp);
+    if (!ok) return 0;
+    if (members) *members = ms.size();
+    if (decoded_bytes) *decoded_bytes = ms.back().dst + ms.back().isize;
+    return 1;
+}

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace fr {
 
 typedef uint8_t u8;
@@ -357,5 +359,19 @@ hipError_t launch_log_aggregate(Table t, DevState* st, const LogEntry* log, u32 
 size_t log_aggregate_temp_bytes();
 hipError_t launch_synth(u8* out, u64 r0, u64 n, int R, u64 seed, const u8* idx1, const u8* idx2, int S, int L1,
                         int L2, hipStream_t s);
+
+// ---- GPU inflate of BGZF files (fr_inflate.hip, fr_feed_bgzf) ------------------------------------
+// One member of a BGZF file whose members all carry FLG == FEXTRA alone: its raw deflate stream is
+// data[in_off, in_off + in_len), decoding to isize bytes at file offset dst with CRC-32 crc (trailer).
+struct BgzfMember {
+    size_t in_off, in_len, dst;
+    u32 isize, crc;
+};
+constexpr u64 BGZF_MAX_IN = 1ull << 30;  // compressed bytes of a BGZF file for the member-parallel paths
+// fr_gz.cpp: the host path's member walk (bgzf_members) and size budget, and as fr_bgzf_probe's walk the
+// extra field must be the BC subfield alone (XLEN 6); false: not such a file
+bool bgzf_member_table(const u8* data, size_t n, std::vector<BgzfMember>& out);
+// fr_deflate.hip: the operator "feed n zero bytes into the raw CRC-32 register", byte-sliced (4 x 256 words)
+void crc_shift_table(u64 n, u32* T);
 
 }  // namespace fr

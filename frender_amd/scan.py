@@ -112,28 +112,45 @@ def _file_done(st, path=None, sample=None):
         raise IndexError("list index out of range")
 
 
-def scan_files(ctx, files, indices, sample, cores, on_file=None, after_file=None):
+def scan_files(ctx, files, indices, sample, cores, on_file=None, after_file=None, gz_reader="host"):
     """scan_file (frender.py:154-181) for files[i], i in `indices` (increasing), into ctx's table.
     The bytes come from the library's native inflate (fr_gz_*): up to `cores` files inflate ahead
     in host threads while the GPU tallies them in order (the reference's Pool over files,
     :189-193).  Every file is opened at its global index, so any subset of a scan's files, on any
     GPU, yields the single-GPU ordinals.  on_file(i, name) runs before a file is read (the
     reference's "Tallying barcodes from ..." line), after_file(i, records, new barcodes) once it is
-    tallied.  Returns {i: (records, new barcodes)}."""
+    tallied.  Returns {i: (records, new barcodes)}.  gz_reader "gpu": BGZF files (fr_bgzf_probe) of a scan
+    without -s are inflated on the GPU (ctx.feed_bgzf) and the pool holds the other files only; a probed
+    file the GPU declines goes through a pool of its own on the spot."""
     out = {}
-    paths = [files[i] for i in indices]
-    pool = _lib.GzPool(paths, threads=max(1, int(cores)), ahead=_lib.inflate_ahead(paths, max(1, int(cores))))
+    on_gpu = {fi for fi in indices if _lib.bgzf_probe(files[fi])[0]} if gz_reader == "gpu" and not sample else set()
+    pooled = [fi for fi in indices if fi not in on_gpu]
+    slot = {fi: k for k, fi in enumerate(pooled)}
+    paths = [files[i] for i in pooled]
+    threads = max(1, int(cores))
+    pool = _lib.GzPool(paths, threads=threads, ahead=_lib.inflate_ahead(paths, threads))
+
+    def feed_pool(p, k, path):
+        try:
+            p.feed(k, ctx)
+        except _lib.GzError as e:  # not a valid gzip stream: the reference's reader fails on it
+            _replay_decode_error(path, sample)
+            raise RuntimeError(f"native inflate rejected {path} but Python's gzip reads it: {e}") from e
+
     try:
-        for k, fi in enumerate(indices):
+        for fi in indices:
             path = files[fi]
             if on_file:
                 on_file(fi, str(os.path.basename(path)))
             ctx.begin_file(sample, file_index=fi)
-            try:
-                pool.feed(k, ctx)
-            except _lib.GzError as e:  # not a valid gzip stream: the reference's reader fails on it
-                _replay_decode_error(path, sample)
-                raise RuntimeError(f"native inflate rejected {path} but Python's gzip reads it: {e}") from e
+            if fi not in on_gpu:
+                feed_pool(pool, slot[fi], path)
+            elif not ctx.feed_bgzf(path)[0]:  # declined (a member failed): the host pool owns the error behaviour
+                one = _lib.GzPool([path], threads=threads, ahead=1)
+                try:
+                    feed_pool(one, 0, path)
+                finally:
+                    one.close()
             st = ctx.end_file()
             _file_done(st, path, sample)
             out[fi] = (int(st.records), int(st.new_keys))
@@ -224,7 +241,7 @@ def build_table(t: dict, names, records) -> UniqueTable:
                        pres_u, pres_f, list(names), list(records), key_of, pres_n)
 
 
-def tally_barcodes(cores, files, sample=None, ctx=None) -> UniqueTable:
+def tally_barcodes(cores, files, sample=None, ctx=None, gz_reader="host") -> UniqueTable:
     """frender.py:183-207 (+ scan_file :154-181) on the GPU: files in order, one context.  With a
     torch.distributed group of N > 1 ranks (one per GPU) the record stream is sharded over the GPUs
     and every rank returns its key partition of the merged table (frender_amd/dist.py:
@@ -246,7 +263,7 @@ def tally_barcodes(cores, files, sample=None, ctx=None) -> UniqueTable:
 
     per = scan_files(ctx, files, list(range(len(files))), sample, cores,
                      on_file=lambda fi, name: print(f"Tallying barcodes from {name}...", end=""),
-                     after_file=lambda fi, records, new: print(found_line(new, records)))
+                     after_file=lambda fi, records, new: print(found_line(new, records)), gz_reader=gz_reader)
     print(type([]), len(files))
     return build_table(local_table(ctx), names, [per[i][0] for i in range(len(files))])
 
@@ -635,7 +652,7 @@ def frender_scan(args, ctx=None) -> dict:
     out_csv_name, spec = output_name(num_subs, user_infix, args.files)
     files = parse_files(spec, just_r1=True)
     ctx = ctx or default_context()
-    table = tally_barcodes(cores, files, sample, ctx=ctx)
+    table = tally_barcodes(cores, files, sample, ctx=ctx, gz_reader=getattr(args, "gz_reader", "host"))
     lead = _lead(table)  # multi-GPU: every rank holds a key partition; rank 0 prints and writes
     if lead:
         print("Scanning complete! Analyzing barcodes...")

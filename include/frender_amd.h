@@ -379,6 +379,47 @@ uint64_t fr_defl_out_bytes(const fr_defl* z);
 uint64_t fr_defl_stored_fallbacks(const fr_defl* z);
 int fr_defl_fetch(fr_defl* z, uint8_t* out, uint64_t len);
 
+/* ---- GPU inflate (fr_inflate.hip): raw deflate streams (RFC 1951) of known decoded size, one wave each.
+ * n raw deflate streams: stream s is bytes [in_off[s], in_off[s+1]) of dev_in and must decode to exactly
+ * out_off[s+1]-out_off[s] bytes (<= 65536, else FR_ERR_INVALID) at dev_out + out_off[s]. status[s]: 0 or a
+ * FR_INFL_* reason; crc32[s]: CRC-32 of the bytes produced (valid when status[s]==0).  Status 0 implies
+ * that zlib accepts the same bytes and produces the same output; a stream may be rejected that zlib would
+ * take only when it is malformed (an incomplete Huffman code set other than a single distance code).  No
+ * input bytes make the decoder read outside its stream or write outside its output range. */
+#define FR_INFL_BTYPE 1   /* block type 3 */
+#define FR_INFL_STORED 2  /* stored LEN != ~NLEN */
+#define FR_INFL_CODELEN 3 /* bad code-length set (over-subscribed, incomplete, bad repeat, no end-of-block code) */
+#define FR_INFL_SYMBOL 4  /* invalid literal/length or distance symbol */
+#define FR_INFL_DIST 5    /* distance before the start of the output */
+#define FR_INFL_INPUT 6   /* input exhausted */
+#define FR_INFL_OVERRUN 7 /* the output would overrun its declared size */
+#define FR_INFL_SHORT 8   /* output short of its declared size, or input left over */
+typedef struct fr_infl fr_infl;
+fr_infl* fr_infl_create(int device);
+void fr_infl_destroy(fr_infl* z);
+const char* fr_infl_last_error(const fr_infl* z);
+int fr_infl_run(fr_infl* z, const uint8_t* dev_in, const uint64_t* in_off, uint8_t* dev_out,
+                const uint64_t* out_off, int n_streams, uint8_t* status, uint32_t* crc32);
+/* the same over a host buffer; the output stays on the device until fr_infl_fetch */
+int fr_infl_run_host(fr_infl* z, const uint8_t* data, const uint64_t* in_off, const uint64_t* out_off,
+                     int n_streams, uint8_t* status, uint32_t* crc32);
+int fr_infl_fetch(fr_infl* z, uint8_t* out, uint64_t len);
+/* diagnostics (scripts/inflate_bench.py): the kernel's registers per lane and LDS per workgroup
+ * (hipFuncGetAttributes) and the last run's kernel time by HIP events (0 before the first run) */
+int fr_infl_kernel_info(fr_infl* z, int* vgprs, int* lds_bytes, double* last_ms);
+/* A BGZF file decoded on the GPU as the current file's whole content (between fr_begin_file[_at] with
+ * byte_base 0 and fr_end_file; replaces gzip.open(file,"rt") at frender.py:159 for such files).
+ * *decoded = 1: every member decoded, its size and CRC-32 equal its trailer, and the bytes went to the
+ * tally as fr_feed_device takes them.  *decoded = 0 (FR_OK, nothing fed, context state untouched): the
+ * file is not BGZF, a member carries header flags other than FEXTRA or extra subfields besides BC, the
+ * file is over the size budget (1 GiB compressed) or its buffers do not fit the device, -s is set, or any
+ * member failed -- the caller feeds the file through the host pool,
+ * which owns the error behaviour.  *members / *bytes: diagnostics. */
+int fr_feed_bgzf(fr_ctx* ctx, const char* path, int* decoded, uint64_t* members, uint64_t* bytes);
+/* headers only, no GPU: 1 when fr_feed_bgzf would try the file (every member's FLG is FEXTRA alone and
+ * its extra field the BC subfield alone, as bgzip and htslib write them; within the size budget) */
+int fr_bgzf_probe(const char* path, uint64_t* members, uint64_t* decoded_bytes);
+
 #ifdef __cplusplus
 }
 #endif
