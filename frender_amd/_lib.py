@@ -917,8 +917,8 @@ class Context:
         return t
 
     def diag(self) -> dict:
-        v = np.zeros(24, dtype=np.uint64)
-        self._ck(lib.fr_get_diag(self.h, _ptr(v), 24), "fr_get_diag")
+        v = np.zeros(26, dtype=np.uint64)
+        self._ck(lib.fr_get_diag(self.h, _ptr(v), 26), "fr_get_diag")
         d = dict(zip(("spin_max", "spin_total", "keys", "overflow", "presence", "exotic", "grid", "slots"),
                      v[:8].tolist()))
         d["spec_replays"] = int(v[16])
@@ -929,6 +929,10 @@ class Context:
         d["fold_max"] = int(v[21])  # the last device feed's fullest launch-log fold (of AGG_LNS = 4096 slots)
         d["fold_over"] = int(v[22])  # its entries that found their fold full
         d["feed_step"] = int(v[23])  # its range size (bytes per launch)
+        # memsets / copies the library queued on its stream since the last reset: each is a blit dispatch of its
+        # own between the kernels, and a steady one-file device-feed step queues none
+        d["stream_fills"] = int(v[24])
+        d["stream_copies"] = int(v[25])
         if v[8:16].any():  # FR_TIMING build / FR_ABLATE=64: per-phase cycles or commit counts
             names = ("guess", "walk0", "wait0", "resolve", "walk1", "commit", "kernel", "chunks")
             d["stamps"] = dict(zip(names, v[8:].tolist()))

@@ -72,10 +72,22 @@ struct fr_ctx {
                                    // bytes 8-15 fr_classify's error flag
     // fr_finalize returns without a host round trip; its live-count check and timing settle at the
     // next call that synchronises (settle_finalize)
-    u64* h_fin = nullptr;          // pinned: the finalize's live-slot count
+    u64* h_fin = nullptr;          // pinned: the finalize's live-slot count (radix path; the binned path reports
+                                   // through h_mir)
+    // The common path's kernels report through this pinned block instead of copy dispatches (fr_internal.h
+    // HostMirror): a device feed's end state and last byte, the finalize's live count, the classify's error flag
+    HostMirror* h_mir = nullptr;
+    HostMirror* d_mir = nullptr;   // its device address
+    // memsets and copies issued on `stream` since the last fr_reset (fill_async / copy_async; fr_get_diag):
+    // each is a blit dispatch of its own between the kernels, and a steady one-file step issues none
+    u64 n_fills = 0, n_copies = 0;
+    bool perfile_clean = false;    // the device's per-file block equals the reset image (no file since fr_reset)
+    bool fold_zero = false;        // DevState::log_fold_max / _over are zero on the device (no logged launch since fr_reset)
+    bool bins_dirty = false;       // d_bins may hold counts (a finalize that failed between its histogram and scatter)
     hipEvent_t fin_e0 = nullptr, fin_e1 = nullptr;
     hipEvent_t cls_e0 = nullptr, cls_e1 = nullptr;  // fr_classify's timing (created once, not per call)
     bool fin_pending = false;
+    bool fin_binned = false;       // the pending finalize's count is h_mir->fin_count (binned order), else *h_fin
     u64 fin_expect = 0;
     bool st_fresh = false;         // h_st equals the device state (no device work on it since)
     Table* d_tab = nullptr;        // device copy of tab for the tally kernel
@@ -217,7 +229,11 @@ struct fr_ctx {
     int16_t *d_m1 = nullptr, *d_m2 = nullptr, *d_row = nullptr, *d_rm2 = nullptr, *d_rrow = nullptr;
     u8 *d_cls = nullptr, *d_rcls = nullptr;
     int32_t* d_errw = nullptr;
+    // two blocks of {error word, rc sums} alternate between fr_classify calls: each launch zeroes the block the
+    // next call will use.  d_errf: both blocks; d_rcf / d_rcr: the sums of the last call's block (fr_rc_counts)
     u64* d_errf = nullptr;
+    u64 errf_words = 0;            // u64 words per block
+    int errf_cur = 0;              // the block the next fr_classify uses (zeroed)
     u64 *d_rcf = nullptr, *d_rcr = nullptr;
     int rc_names_cap = 0;
 
@@ -262,20 +278,22 @@ static u64 pow2_at_least(u64 x) {
     return p;
 }
 
-static int state_reset_counts(fr_ctx* ctx) {
-    // the device copy comes from a pinned image that never changes, so nothing waits for it; the
-    // host snapshot is overwritten only once no asynchronous snapshot can still land on it
-    if (ctx->st_pending) CK(hipStreamSynchronize(ctx->stream));
-    *ctx->h_st = *ctx->h_zero;
-    CK(hipMemcpyAsync(ctx->st, ctx->h_zero, sizeof(DevState), hipMemcpyHostToDevice, ctx->stream));
-    ctx->st_pending = false;
-    ctx->st_fresh = true;
-    return FR_OK;
+// every memset / copy on ctx->stream goes through these two: the runtime turns each into a blit kernel of
+// its own (4-6 us, two per memset), serialised between ours, so the common path issues none and the counts
+// (fr_get_diag) let a test hold it to that
+static hipError_t fill_async(fr_ctx* ctx, void* dst, int value, size_t bytes) {
+    ctx->n_fills++;
+    return hipMemsetAsync(dst, value, bytes, ctx->stream);
+}
+
+static hipError_t copy_async(fr_ctx* ctx, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    ctx->n_copies++;
+    return hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);
 }
 
 static int read_state(fr_ctx* ctx) {  // exact snapshot (a host round trip only when stale)
     if (ctx->st_fresh && !ctx->st_pending) return FR_OK;
-    CK(hipMemcpyAsync(ctx->h_st, ctx->st, sizeof(DevState), hipMemcpyDeviceToHost, ctx->stream));
+    CK(copy_async(ctx, ctx->h_st, ctx->st, sizeof(DevState), hipMemcpyDeviceToHost));
     CK(hipStreamSynchronize(ctx->stream));
     ctx->st_pending = false;
     ctx->st_fresh = true;
@@ -294,7 +312,7 @@ static int grow_table(fr_ctx* ctx, bool force_bigger) {
         if (ns == ctx->nslots) ns <<= 1;
         GSlot* ns_slots = nullptr;
         CK(dalloc(&ns_slots, ns));
-        CK(launch_table_init(ns_slots, ns, ctx->stream));
+        CK(launch_table_init(ns_slots, ns, nullptr, ctx->stream));
         Table t = ctx->tab;
         t.slots = ns_slots;
         t.mask = ns - 1;
@@ -309,7 +327,7 @@ static int grow_table(fr_ctx* ctx, bool force_bigger) {
         Overflow* fresh = nullptr;
         CK(dalloc(&fresh, ctx->tab.ovf_cap));
         ctx->tab.ovf = fresh;
-        CK(hipMemsetAsync(&ctx->st->n_overflow, 0, sizeof(u64), ctx->stream));
+        CK(fill_async(ctx, &ctx->st->n_overflow, 0, sizeof(u64)));
         CK(launch_reinsert_overflow(ctx->tab, ctx->st, old, novf, ctx->stream));
         ctx->st_fresh = false;
         CK(hipStreamSynchronize(ctx->stream));
@@ -328,8 +346,8 @@ static int ensure_presence_cap(fr_ctx* ctx) {
     while (ncap < need * 2) ncap *= 2;
     Presence* np = nullptr;
     CK(dalloc(&np, ncap));
-    CK(hipMemcpyAsync(np, ctx->tab.pres, std::min(ctx->h_st->n_presence, ctx->tab.pres_cap) * sizeof(Presence),
-                      hipMemcpyDeviceToDevice, ctx->stream));
+    CK(copy_async(ctx, np, ctx->tab.pres, std::min(ctx->h_st->n_presence, ctx->tab.pres_cap) * sizeof(Presence),
+                      hipMemcpyDeviceToDevice));
     CK(hipStreamSynchronize(ctx->stream));
     CK(hipFree(ctx->tab.pres));
     ctx->tab.pres = np;
@@ -365,14 +383,26 @@ static int maybe_grow(fr_ctx* ctx) {
 }
 
 static int snapshot_async(fr_ctx* ctx) {
-    CK(hipMemcpyAsync(ctx->h_st, ctx->st, sizeof(DevState), hipMemcpyDeviceToHost, ctx->stream));
+    CK(copy_async(ctx, ctx->h_st, ctx->st, sizeof(DevState), hipMemcpyDeviceToHost));
     CK(hipEventRecord(ctx->st_ev, ctx->stream));
     ctx->st_pending = true;
     return FR_OK;
 }
 
+// after a mirrored launch (launch_range): wait for it and take the state it left in the pinned block --
+// an exact snapshot, as read_state's, without a copy dispatch (earlier ranges' asynchronous snapshots are
+// ahead of it in stream order, so they have landed too)
+static int take_mirror(fr_ctx* ctx) {
+    CK(hipStreamSynchronize(ctx->stream));
+    *ctx->h_st = ctx->h_mir->st;
+    ctx->st_pending = false;
+    ctx->st_fresh = true;
+    return FR_OK;
+}
+
 // the last fr_finalize's check: every live slot was counted once (its pinned count has landed once
-// fin_e1 has: the copy is queued before the event), and its device time
+// fin_e1 has: fin_scatter_kernel's store into the pinned block -- on the radix path the counter's copy --
+// is ahead of the event in stream order), and its device time
 static int settle_finalize(fr_ctx* ctx) {
     if (!ctx->fin_pending) return FR_OK;
     ctx->fin_pending = false;
@@ -380,7 +410,8 @@ static int settle_finalize(fr_ctx* ctx) {
     float ms = 0;
     if (ctx->fin_timed) CK(hipEventElapsedTime(&ms, ctx->fin_e0, ctx->fin_e1));
     ctx->finalize_ms = ms;
-    if (*ctx->h_fin != ctx->fin_expect) return fail(ctx, FR_ERR_DEVICE, "compaction count mismatch");
+    const u64 counted = ctx->fin_binned ? ctx->h_mir->fin_count : *ctx->h_fin;
+    if (counted != ctx->fin_expect) return fail(ctx, FR_ERR_DEVICE, "compaction count mismatch");
     return FR_OK;
 }
 
@@ -388,7 +419,7 @@ static int upload_table(fr_ctx* ctx) {
     if (std::memcmp(&ctx->tab, ctx->h_tab, sizeof(Table)) != 0) {  // the table moved: refresh its device copy
         CK(hipStreamSynchronize(ctx->stream));  // the previous copy from h_tab has landed
         std::memcpy(ctx->h_tab, &ctx->tab, sizeof(Table));
-        CK(hipMemcpyAsync(ctx->d_tab, ctx->h_tab, sizeof(Table), hipMemcpyHostToDevice, ctx->stream));
+        CK(copy_async(ctx, ctx->d_tab, ctx->h_tab, sizeof(Table), hipMemcpyHostToDevice));
     }
     return FR_OK;
 }
@@ -432,11 +463,11 @@ static int drain_exotic(fr_ctx* ctx) {
     std::vector<u64> ord(n), off(n);
     std::vector<u32> len(n);
     std::vector<u8> pool(used);
-    CK(hipMemcpyAsync(ord.data(), ctx->tab.exo_ord, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipMemcpyAsync(off.data(), ctx->tab.exo_off, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipMemcpyAsync(len.data(), ctx->tab.exo_len, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (used) CK(hipMemcpyAsync(pool.data(), ctx->tab.exo_pool, used, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipMemsetAsync(&ctx->st->n_exotic, 0, 2 * sizeof(u64), ctx->stream));  // n_exotic, exo_pool_used
+    CK(copy_async(ctx, ord.data(), ctx->tab.exo_ord, n * 8, hipMemcpyDeviceToHost));
+    CK(copy_async(ctx, off.data(), ctx->tab.exo_off, n * 8, hipMemcpyDeviceToHost));
+    CK(copy_async(ctx, len.data(), ctx->tab.exo_len, n * 4, hipMemcpyDeviceToHost));
+    if (used) CK(copy_async(ctx, pool.data(), ctx->tab.exo_pool, used, hipMemcpyDeviceToHost));
+    CK(fill_async(ctx, &ctx->st->n_exotic, 0, 2 * sizeof(u64)));  // n_exotic, exo_pool_used
     CK(hipStreamSynchronize(ctx->stream));
     s.n_exotic = 0;
     s.exo_pool_used = 0;
@@ -485,16 +516,17 @@ static int replay_exotic(fr_ctx* ctx) {
     s.n_exotic = 0;
     s.exo_pool_used = 0;
     s.cap_flags &= ~4u;
-    CK(hipMemsetAsync(&ctx->st->n_exotic, 0, 2 * sizeof(u64), ctx->stream));
-    CK(hipMemcpyAsync(&ctx->st->cap_flags, &s.cap_flags, sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+    CK(fill_async(ctx, &ctx->st->n_exotic, 0, 2 * sizeof(u64)));
+    CK(copy_async(ctx, &ctx->st->cap_flags, &s.cap_flags, sizeof(u32), hipMemcpyHostToDevice));
     ScanArgs a = ctx->last_args;
     a.exo_only = 1;
     a.spec_commit = 0;
+    a.zero_fold = 0;  // (the fold statistics are the aggregation's: a replay leaves them)
     a.log = nullptr;
     a.epoch = ++ctx->epoch;
     a.tab = ctx->d_tab;
     a.tabv = ctx->tab;
-    CK(hipMemsetAsync(&ctx->st->ticket, 0, 2 * sizeof(u32), ctx->stream));  // ticket, chunks_done
+    CK(fill_async(ctx, &ctx->st->ticket, 0, 2 * sizeof(u32)));  // ticket, chunks_done
     rc = launch_args(ctx, a, ctx->last_grid);
     if (rc) return rc;
     ctx->exo_replays++;
@@ -523,8 +555,11 @@ static int launch_args(fr_ctx* ctx, const ScanArgs& a, int grid) {  // the calle
     return FR_OK;
 }
 
+// mirror: a device feed's last range.  A logged launch's aggregation then mirrors the device state and the
+// range's last byte into ctx->h_mir (the caller synchronises and takes them: take_mirror) and *mirrored is
+// set; a launch without a log leaves the state read to the caller.  zero_fold: ScanArgs::zero_fold.
 static int launch_range(fr_ctx* ctx, const u8* dptr, u64 len, u64 avail, int own_start, int own_end, int pre_valid,
-                        int exo_only = 0) {
+                        int exo_only = 0, bool mirror = false, bool* mirrored = nullptr, bool zero_fold = false) {
     if (len == 0) return FR_OK;
     int rc = FR_OK;
     if (ctx->host_feed && ctx->last_valid) {
@@ -555,12 +590,13 @@ static int launch_range(fr_ctx* ctx, const u8* dptr, u64 len, u64 avail, int own
     a.chunk_info = ctx->chunk_info;
     a.spec_commit = exo_only ? 0u : ctx->spec_commit;
     a.exo_only = (u32)exo_only;
+    a.zero_fold = zero_fold ? 1u : 0u;
     rc = upload_table(ctx);
     if (rc) return rc;
     a.tab = ctx->d_tab;
     a.tabv = ctx->tab;
     if (ctx->epoch >= 0x7FFFFFFFu) {  // tag wrap: restart epochs on a cleared descriptor array
-        CK(hipMemsetAsync(ctx->tiles, 0, ctx->tiles_cap * sizeof(u64), ctx->stream));
+        CK(fill_async(ctx, ctx->tiles, 0, ctx->tiles_cap * sizeof(u64)));
         ctx->epoch = 1;
         a.epoch = 1;
     }
@@ -628,9 +664,12 @@ static int launch_range(fr_ctx* ctx, const u8* dptr, u64 len, u64 avail, int own
     ctx->last_grid = grid;
     ctx->last_valid = true;
     if (timed) CK(hipEventRecord(ctx->ev_b[ctx->ev_used], ctx->stream));
-    if (a.log)
+    const bool mir = mirror && a.log;
+    if (a.log) {
         CK(launch_log_aggregate(ctx->tab, ctx->st, ctx->log, ctx->log_rcap, ctx->log_sub, ctx->log_scap, a.file_tag,
-                                a.file_offset, ctx->stream));
+                                a.file_offset, mir ? ctx->d_mir : nullptr, mir ? dptr + len - 1 : nullptr, ctx->stream));
+        ctx->fold_zero = false;
+    }
     if (timed) {
         CK(hipEventRecord(ctx->ev_l[ctx->ev_used], ctx->stream));
         ctx->ev_used++;
@@ -640,6 +679,10 @@ static int launch_range(fr_ctx* ctx, const u8* dptr, u64 len, u64 avail, int own
     ctx->par ^= 1u;
     ctx->file_offset += len;
     ctx->max_file_bytes = std::max(ctx->max_file_bytes, ctx->file_offset);  // bounds every ordinal's offset
+    if (mir) {  // the state reaches the host through the mirror: no snapshot copy behind the launch
+        *mirrored = true;
+        return FR_OK;
+    }
     return snapshot_async(ctx);
 }
 
@@ -737,6 +780,10 @@ fr_ctx* fr_create_tuned(int device, uint64_t chunk_bytes, uint64_t table_slots, 
         return bad("pinned state", e);
     if ((e = hipHostMalloc((void**)&ctx->h_byte, 64, hipHostMallocDefault)) != hipSuccess) return bad("pinned byte", e);
     if ((e = hipHostMalloc((void**)&ctx->h_fin, 64, hipHostMallocDefault)) != hipSuccess) return bad("pinned count", e);
+    if ((e = hipHostMalloc((void**)&ctx->h_mir, sizeof(HostMirror), hipHostMallocDefault)) != hipSuccess)
+        return bad("pinned mirror", e);
+    std::memset(ctx->h_mir, 0, sizeof(HostMirror));
+    if ((e = hipHostGetDevicePointer((void**)&ctx->d_mir, ctx->h_mir, 0)) != hipSuccess) return bad("pinned mirror", e);
     if ((e = hipEventCreate(&ctx->fin_e0)) != hipSuccess) return bad("event", e);
     if ((e = hipEventCreate(&ctx->fin_e1)) != hipSuccess) return bad("event", e);
     if ((e = hipEventCreate(&ctx->cls_e0)) != hipSuccess) return bad("event", e);
@@ -795,6 +842,7 @@ void fr_destroy(fr_ctx* ctx) {
     if (ctx->h_zero) (void)hipHostFree(ctx->h_zero);
     if (ctx->h_byte) (void)hipHostFree(ctx->h_byte);
     if (ctx->h_fin) (void)hipHostFree(ctx->h_fin);
+    if (ctx->h_mir) (void)hipHostFree(ctx->h_mir);
     if (ctx->fin_e0) (void)hipEventDestroy(ctx->fin_e0);
     if (ctx->fin_e1) (void)hipEventDestroy(ctx->fin_e1);
     if (ctx->cls_e0) (void)hipEventDestroy(ctx->cls_e0);
@@ -826,7 +874,8 @@ int fr_get_diag(fr_ctx* ctx, uint64_t* out, int n) {
                           (uint64_t)ctx->grid, ctx->nslots, s.stamp[0], s.stamp[1], s.stamp[2], s.stamp[3],
                           s.stamp[4],  s.stamp[5],  s.stamp[6], s.stamp[7], ctx->spec_replays, ctx->exo_replays,
                           s.heavy[ctx->par] ? ctx->chunk_tiles_heavy : ctx->chunk_tiles,  // the next ramped launch's
-                          s.heavy_launches, ctx->big_rollbacks, ctx->feed_fold_max, ctx->feed_fold_over, ctx->feed_step};
+                          s.heavy_launches, ctx->big_rollbacks, ctx->feed_fold_max, ctx->feed_fold_over, ctx->feed_step,
+                          ctx->n_fills, ctx->n_copies};  // (new entries go at the end: the indices are the ABI)
     for (int i = 0; i < n && i < (int)(sizeof(v) / sizeof(v[0])); ++i) out[i] = v[i];
     return FR_OK;
 }
@@ -923,7 +972,7 @@ int fr_set_sheet(fr_ctx* ctx, int S, const uint64_t* idx1_packed, const int32_t*
         std::memcpy(ctx->h_sheet, h, total);
         ctx->sheet_bytes = total;
         ++ctx->sheet_ver;
-        CK(hipMemcpyAsync(ctx->d_sheet, ctx->h_sheet, total, hipMemcpyHostToDevice, ctx->stream));
+        CK(copy_async(ctx, ctx->d_sheet, ctx->h_sheet, total, hipMemcpyHostToDevice));
     }
     u8* d = ctx->d_sheet;
     ctx->d_i1 = (u64*)d;
@@ -954,9 +1003,15 @@ int fr_reset(fr_ctx* ctx) {
     if (int src = settle_finalize(ctx)) return src;
     CK(hipSetDevice(ctx->device));
     CK(hipStreamSynchronize(ctx->copy));
-    CK(launch_table_init(ctx->tab.slots, ctx->nslots, ctx->stream));
-    int rc = state_reset_counts(ctx);
-    if (rc) return rc;
+    ctx->n_fills = ctx->n_copies = 0;
+    // the host snapshot is overwritten only once no asynchronous snapshot can still land on it; the device
+    // state takes its reset image from the table clear itself (no upload dispatch)
+    if (ctx->st_pending) CK(hipStreamSynchronize(ctx->stream));
+    CK(launch_table_init(ctx->tab.slots, ctx->nslots, ctx->st, ctx->stream));
+    *ctx->h_st = *ctx->h_zero;
+    ctx->st_fresh = true;
+    ctx->perfile_clean = true;
+    ctx->fold_zero = true;
     ctx->scanning = true;
     ctx->file_open = false;
     ctx->file_tag = 0;
@@ -1003,7 +1058,9 @@ int fr_begin_file_at(fr_ctx* ctx, int64_t file_index, uint64_t byte_base, int64_
     ctx->last_valid = false;
     // per-file device flags + line carry: DevState's per-file block, from the pinned reset image
     static_assert(offsetof(DevState, utf8_bad) + sizeof(u32) - offsetof(DevState, lines) == 32, "per-file block");
-    CK(hipMemcpyAsync(&ctx->st->lines[0], &ctx->h_zero->lines[0], 32, hipMemcpyHostToDevice, ctx->stream));
+    // (the first file after fr_reset finds the block as the reset left it: no upload)
+    if (!ctx->perfile_clean) CK(copy_async(ctx, &ctx->st->lines[0], &ctx->h_zero->lines[0], 32, hipMemcpyHostToDevice));
+    ctx->perfile_clean = false;
     ctx->h_st->lines[0] = ctx->h_st->lines[1] = 0;  // the snapshot stays exact
     ctx->h_st->err_nospace = ~0ull;
     ctx->h_st->nonascii = ctx->h_st->utf8_bad = 0;
@@ -1111,7 +1168,7 @@ int fr_feed_device(fr_ctx* ctx, const uint8_t* dev_data, uint64_t len) {
             ctx->snap_cap = snap_slots;
         }
         snap = ctx->snap;
-        CK(hipMemcpyAsync(snap, ctx->tab.slots, snap_slots * sizeof(GSlot), hipMemcpyDeviceToDevice, ctx->stream));
+        CK(copy_async(ctx, snap, ctx->tab.slots, snap_slots * sizeof(GSlot), hipMemcpyDeviceToDevice));
     }
     // Equal ranges of at most chunk_bytes: one launch (one set of ramps and tail) for the bench's 7.4 GB,
     // DESIGN.md §4.1.  The table grows between launches, never inside one, so a range over RANGE_FIRST_MAX is
@@ -1132,9 +1189,12 @@ int fr_feed_device(fr_ctx* ctx, const uint8_t* dev_data, uint64_t len) {
                (saved.n_keys + ctx->feed_keys) * 2 <= ctx->nslots;
     bool spec_now = spec;
     u64 step = 0, lim_room = ~0ull;
+    int last_b = -1;
     for (int attempt = 0; attempt < 12; ++attempt) {
-        // the attempt's fold statistics start at zero (a rollback restores the state before the feed)
-        CK(hipMemsetAsync(&ctx->st->log_fold_max, 0, 2 * sizeof(u32), ctx->stream));
+        // the attempt's fold statistics start at zero (a rollback restores the state before the feed): they are
+        // zero since fr_reset until a launch logs, else the attempt's first launch zeroes them (ScanArgs::zero_fold)
+        const bool zero_fold = !ctx->fold_zero;
+        bool mirrored = false;
         const u64 lim = std::min<u64>(big ? ctx->chunk_bytes : std::min<u64>(ctx->chunk_bytes, RANGE_FIRST_MAX),
                                       lim_room);
         const u64 nr = (len + lim - 1) / lim;
@@ -1142,13 +1202,21 @@ int fr_feed_device(fr_ctx* ctx, const uint8_t* dev_data, uint64_t len) {
         ctx->spec_commit = spec_now ? 1u : 0u;
         for (u64 off = 0; off < len; off += step) {
             const u64 n = std::min<u64>(step, len - off);
-            rc = launch_range(ctx, dev_data + off, n, len - off, off == 0 ? 1 : 0, 1, off ? 1 : 0);
+            rc = launch_range(ctx, dev_data + off, n, len - off, off == 0 ? 1 : 0, 1, off ? 1 : 0, 0,
+                              /*mirror=*/off + n == len, &mirrored, zero_fold && off == 0);
             if (rc) break;
         }
         ctx->spec_commit = 0;
-        // the feed's last byte lands with the state read below (one host round trip for both)
-        if (!rc && len) CK(hipMemcpyAsync(ctx->h_byte, dev_data + len - 1, 1, hipMemcpyDeviceToHost, ctx->stream));
-        if (!rc) rc = read_state(ctx);
+        // the feed's end state and last byte reach the host with one round trip: through the pinned mirror,
+        // written by the last launch's aggregation, or (launches without a log) by two copies
+        if (!rc && mirrored) {
+            rc = take_mirror(ctx);
+            last_b = (int)(ctx->h_mir->last_byte & 0xFFu);
+        } else if (!rc) {
+            if (len) CK(copy_async(ctx, ctx->h_byte, dev_data + len - 1, 1, hipMemcpyDeviceToHost));
+            rc = read_state(ctx);
+            if (!rc && len) last_b = *ctx->h_byte;  // landed: read_state synchronised after the copy
+        }
         if (rc) break;
         const bool spec_bad = spec_now && ctx->h_st->spec_fail;
         // the overflow list ran out (fr_end_file would report FR_ERR_CAPACITY): smaller ranges, if any left
@@ -1173,13 +1241,14 @@ int fr_feed_device(fr_ctx* ctx, const uint8_t* dev_data, uint64_t len) {
             ctx->tab.mask = snap_slots - 1;
             ctx->nslots = snap_slots;
         }
-        if (empty) CK(launch_table_init(ctx->tab.slots, ctx->nslots, ctx->stream));
-        else CK(hipMemcpyAsync(ctx->tab.slots, snap, snap_slots * sizeof(GSlot), hipMemcpyDeviceToDevice, ctx->stream));
+        if (empty) CK(launch_table_init(ctx->tab.slots, ctx->nslots, nullptr, ctx->stream));
+        else CK(copy_async(ctx, ctx->tab.slots, snap, snap_slots * sizeof(GSlot), hipMemcpyDeviceToDevice));
         *ctx->h_st = saved;
-        CK(hipMemcpyAsync(ctx->st, ctx->h_st, sizeof(DevState), hipMemcpyHostToDevice, ctx->stream));
+        CK(copy_async(ctx, ctx->st, ctx->h_st, sizeof(DevState), hipMemcpyHostToDevice));
         CK(hipStreamSynchronize(ctx->stream));
         ctx->st_pending = false;
         ctx->st_fresh = true;
+        ctx->fold_zero = false;  // (the restored state carries the fold statistics of the feed before this one)
         ctx->par = par0;
         ctx->file_offset = ctx->file_base;
         if (!room_bad) ctx->spec_replays++;
@@ -1203,7 +1272,7 @@ int fr_feed_device(fr_ctx* ctx, const uint8_t* dev_data, uint64_t len) {
         s.exo_pool_used = 0;
         s.cap_flags &= ~4u;
         s.lines[par0] = saved.lines[par0];
-        CK(hipMemcpyAsync(ctx->st, ctx->h_st, sizeof(DevState), hipMemcpyHostToDevice, ctx->stream));
+        CK(copy_async(ctx, ctx->st, ctx->h_st, sizeof(DevState), hipMemcpyHostToDevice));
         ctx->par = par0;
         ctx->file_offset = ctx->file_base;
         ctx->exo_replays++;
@@ -1219,7 +1288,7 @@ int fr_feed_device(fr_ctx* ctx, const uint8_t* dev_data, uint64_t len) {
     }
     rc = drain_exotic(ctx);
     if (rc) return rc;
-    if (len) ctx->last_byte = *ctx->h_byte;  // landed: read_state synchronised after the copy
+    if (len) ctx->last_byte = last_b;
     ctx->carry.clear();
     return FR_OK;
 }
@@ -1385,6 +1454,7 @@ int fr_finalize(fr_ctx* ctx, uint64_t* n_unique, uint64_t* n_presence, uint64_t*
             CK(hipMalloc(&ctx->d_bins, cap * sizeof(u32)));
             CK(hipMalloc(&ctx->d_binbase, cap * sizeof(u32)));
             ctx->bins_cap = cap;
+            ctx->bins_dirty = true;  // zeroed once, below; from then on its last reader leaves it zeroed
         }
         size_t need = 0;
         CK(launch_fin_scan(ctx->d_bins, ctx->d_binbase, nbins + 1, nullptr, &need, ctx->stream));
@@ -1396,14 +1466,20 @@ int fr_finalize(fr_ctx* ctx, uint64_t* n_unique, uint64_t* n_presence, uint64_t*
         size_t tb = ctx->temp_bytes;
         // the slots' uidx is read only by presence_map_kernel: a one-file scan (deferred presence) skips it
         const bool set_uidx = ctx->pres_defer_tag == 0;
-        CK(hipMemsetAsync(ctx->d_bins, 0, (nbins + 1) * sizeof(u32), ctx->stream));
+        // d_bins is all zero here: fin_scatter_kernel zeroes the nbins + 1 counts its finalize used (no memset
+        // dispatch per call).  Only a fresh array, or one a failed call left between the two, is cleared whole
+        if (ctx->bins_dirty) CK(fill_async(ctx, ctx->d_bins, 0, ctx->bins_cap * sizeof(u32)));
+        ctx->bins_dirty = true;
         CK(launch_fin_hist(ctx->tab.slots, ctx->nslots, bm, ctx->d_bins, ctx->d_arr, ctx->stream));
         CK(launch_fin_scan(ctx->d_bins, ctx->d_binbase, nbins + 1, ctx->d_temp, &tb, ctx->stream));
-        CK(launch_fin_scatter(ctx->tab.slots, ctx->nslots, bm, ctx->d_binbase, ctx->d_arr, ctx->d_rows, ctx->stream));
+        ctx->h_mir->fin_count = 0;
+        CK(launch_fin_scatter(ctx->tab.slots, ctx->nslots, bm, ctx->d_binbase, ctx->d_arr, ctx->d_rows, ctx->d_bins,
+                              &ctx->d_mir->fin_count, ctx->stream));
+        ctx->bins_dirty = false;
         CK(launch_fin_rank(ctx->tab.slots, nk, bm, ctx->d_binbase, ctx->d_rows, ctx->d_keys_s, ctx->d_counts_s,
                            ctx->d_first_s, set_uidx, ctx->stream));
     } else {
-        CK(hipMemsetAsync(ctx->d_counter, 0, sizeof(u64), ctx->stream));
+        CK(fill_async(ctx, ctx->d_counter, 0, sizeof(u64)));
         CK(launch_compact(ctx->tab.slots, ctx->nslots, ctx->d_keys, ctx->d_counts, ctx->d_first, ctx->d_pos,
                           ctx->d_counter, ctx->stream));
         // ordinals are < (file_tag + 1) << ORD_SHIFT: sort only the bits that can be set.  Without
@@ -1453,11 +1529,11 @@ int fr_finalize(fr_ctx* ctx, uint64_t* n_unique, uint64_t* n_presence, uint64_t*
     else
         CK(launch_presence_map(ctx->tab.slots, ctx->tab.mask, ctx->tab.pres, np, ctx->d_pres_u, ctx->d_pres_f,
                                ctx->d_pres_c, ctx->stream));
+    // every live slot counted once: the bin scan's last entry is in the pinned mirror already
+    // (fin_scatter_kernel); the radix path copies its counter
+    ctx->fin_binned = nbins != 0;
     *ctx->h_fin = 0;
-    if (nbins)  // the scan's last entry: every live slot counted once
-        CK(hipMemcpyAsync(ctx->h_fin, ctx->d_binbase + nbins, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    else
-        CK(hipMemcpyAsync(ctx->h_fin, ctx->d_counter, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    if (!nbins) CK(copy_async(ctx, ctx->h_fin, ctx->d_counter, sizeof(u64), hipMemcpyDeviceToHost));
     CK(hipEventRecord(e1, ctx->stream));
     ctx->fin_pending = true;
     ctx->fin_expect = nk;
@@ -1556,11 +1632,14 @@ static int ensure_class_scratch(fr_ctx* ctx, u64 n) {
     CK(dalloc(&ctx->d_cls, cap));
     CK(dalloc(&ctx->d_rcls, cap));
     CK(dalloc(&ctx->d_errw, cap));
-    // one block zeroed by one memset per classify: ~(first error index) (0: none), then the rc sums
+    // two blocks of ~(first error index) (0: none) then the rc sums: zeroed here once, then each classify
+    // launch zeroes the block the next call uses
     const int names = std::max(ctx->n_names, 1);
-    CK(dalloc(&ctx->d_errf, 1 + 2 * (u64)names));
-    ctx->d_rcf = ctx->d_errf + 1;
-    ctx->d_rcr = ctx->d_rcf + names;
+    ctx->errf_words = 1 + 2 * (u64)names;
+    CK(dalloc(&ctx->d_errf, 2 * ctx->errf_words));
+    CK(fill_async(ctx, ctx->d_errf, 0, 2 * ctx->errf_words * 8));
+    ctx->errf_cur = 0;
+    ctx->d_rcf = ctx->d_rcr = nullptr;  // no rc classify on these blocks yet
     ctx->ccap = cap;
     ctx->rc_names_cap = names;
     return FR_OK;
@@ -1600,7 +1679,7 @@ static int ensure_nbr(fr_ctx* ctx, const SheetArgs& sh, int nsubs, int rc) {
     m.mmask[0] = (u32)(n1 - 1);
     m.mmask[1] = m.mmask[2] = (u32)(n2 - 1);
     m.pmask[0] = m.pmask[1] = (u32)(np - 1);
-    CK(hipMemsetAsync(ctx->d_nbr, 0, bytes, ctx->stream));
+    CK(fill_async(ctx, ctx->d_nbr, 0, bytes));
     CK(launch_nbr_build(sh, ctx->d_canon, nsubs, rc, m, ctx->stream));
     m.on = 1;
     return FR_OK;
@@ -1613,21 +1692,34 @@ int fr_classify(fr_ctx* ctx, int num_subs, int rc_mode, int16_t* m1, int16_t* m2
     int rc = ensure_class_scratch(ctx, n);
     if (rc) return rc;
     hipEvent_t e0 = ctx->cls_e0, e1 = ctx->cls_e1;
-    // the whole block: d_rcr sits rc_names_cap entries after d_rcf, however many names this sheet has
-    CK(hipMemsetAsync(ctx->d_errf, 0, (1 + 2 * (u64)ctx->rc_names_cap) * 8, ctx->stream));
+    // this call's block (zero: the previous launch, or the allocation, cleared it) and the next call's, which
+    // this launch clears whole; d_rcr sits rc_names_cap entries after d_rcf, however many names this sheet has
+    u64* blk = ctx->d_errf + (u64)ctx->errf_cur * ctx->errf_words;
+    u64* next = ctx->d_errf + (u64)(ctx->errf_cur ^ 1) * ctx->errf_words;
     SheetArgs sh{ctx->S, ctx->n_names, ctx->L1u, ctx->L2u, ctx->d_i1, ctx->d_i2, ctx->d_i2rc, ctx->d_name};
     if ((rc = ensure_nbr(ctx, sh, num_subs, rc_mode ? 1 : 0))) return rc;
     ClassOut o{ctx->d_m1, ctx->d_m2, ctx->d_cls, ctx->d_row, ctx->d_rm2, ctx->d_rcls, ctx->d_rrow,
-               ctx->d_rcf, ctx->d_rcr, ctx->d_errf, ctx->d_errw};
+               blk + 1, blk + 1 + ctx->rc_names_cap, blk, ctx->d_errw};
     const bool timed = ctx->timing;
     if (timed) CK(hipEventRecord(e0, ctx->stream));
-    CK(launch_classify(ctx->d_keys_s, ctx->d_counts_s, n, sh, num_subs, rc_mode ? 1 : 0, o, ctx->nbr, ctx->stream));
+    ctx->h_mir->err_flag = 0;
+    CK(launch_classify(ctx->d_keys_s, ctx->d_counts_s, n, sh, num_subs, rc_mode ? 1 : 0, o, ctx->nbr, next,
+                       (u32)ctx->errf_words, &ctx->d_mir->err_flag, ctx->stream));
+    ctx->errf_cur ^= 1;
+    ctx->d_rcf = o.rc_f;  // fr_rc_counts reads this call's sums until the next one
+    ctx->d_rcr = o.rc_r;
     if (timed) CK(hipEventRecord(e1, ctx->stream));
-    // (into pinned memory: a pageable destination makes the copy a staged, synchronous one)
-    CK(hipMemcpyAsync(ctx->h_byte + 8, ctx->d_errf, 8, hipMemcpyDeviceToHost, ctx->stream));  // ~index, 0 none
+    // the pinned flag says whether any code had an error: only then is the exact word (~index) copied back.
+    // (A last-workgroup report of the word itself was measured: its per-workgroup release fence and counter
+    // atomic more than doubled the kernel, 42 -> 90 us at 1.4M codes.)
     CK(hipStreamSynchronize(ctx->stream));
-    u64 ef;
-    std::memcpy(&ef, ctx->h_byte + 8, 8);
+    u64 ef = 0;
+    if (ctx->h_mir->err_flag) {
+        // (into pinned memory: a pageable destination makes the copy a staged, synchronous one)
+        CK(copy_async(ctx, ctx->h_byte + 8, blk, 8, hipMemcpyDeviceToHost));
+        CK(hipStreamSynchronize(ctx->stream));
+        std::memcpy(&ef, ctx->h_byte + 8, 8);
+    }
     ef = ~ef;  // the kernel kept ~(first error index): 0 -> ~0, none
     if (int src = settle_finalize(ctx)) return src;  // landed with the classify: no extra round trip
     float ms = 0;
@@ -1720,9 +1812,9 @@ int fr_export_unique_device(fr_ctx* ctx, void* dev_keys, void* dev_counts, void*
     if (int src = settle_finalize(ctx)) return src;
     if (ctx->U > cap) return fail(ctx, FR_ERR_CAPACITY, "export buffer too small");
     if (ctx->U) {
-        CK(hipMemcpyAsync(dev_keys, ctx->d_keys_s, ctx->U * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        CK(hipMemcpyAsync(dev_counts, ctx->d_counts_s, ctx->U * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        CK(hipMemcpyAsync(dev_first, ctx->d_first_s, ctx->U * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        CK(copy_async(ctx, dev_keys, ctx->d_keys_s, ctx->U * 8, hipMemcpyDeviceToDevice));
+        CK(copy_async(ctx, dev_counts, ctx->d_counts_s, ctx->U * 8, hipMemcpyDeviceToDevice));
+        CK(copy_async(ctx, dev_first, ctx->d_first_s, ctx->U * 8, hipMemcpyDeviceToDevice));
     }
     CK(hipStreamSynchronize(ctx->stream));
     return FR_OK;

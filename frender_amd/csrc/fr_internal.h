@@ -158,6 +158,18 @@ struct DevState {
     u32 log_fold_over;   // entries that found their sub-region's fold full (inserted on their own)
 };
 
+// The pinned, device-visible host block through which the common path's kernels report to the host
+// (fr_api.hip): written with plain stores and a system-scope fence by a launch's last workgroup, read by
+// the host after it has synchronised the stream -- no copy dispatch of its own.
+struct HostMirror {
+    DevState st;         // log_reduce_kernel, a device feed's last launch: the state after the launch (the words
+                         // that are zero after every aggregation -- log cursors, log_n, log_red_done -- are the host's)
+    u32 last_byte;       // ... and the feed's last byte
+    // (a cache line each: the host zeroes a word of its own while another kernel's may still be on its way)
+    alignas(64) u64 fin_count;  // fin_scatter_kernel: the bin scan's last entry (every live slot counted once)
+    alignas(64) u64 err_flag;   // classify_kernel: nonzero when some code had an error (the host then reads the exact word)
+};
+
 struct Table {
     GSlot* slots;
     u64 mask;
@@ -213,6 +225,8 @@ struct ScanArgs {
                          // table updates), every chunk with its exact line phase
     u32 spec_commit;     // commit speculative chunks without waiting for their exact prefix (checked at the
                          // launch end by verify_launch; a wrong guess sets spec_fail)
+    u32 zero_fold;       // a device feed's first launch when the fold statistics (DevState::log_fold_max, _over) may
+                         // hold an earlier feed's: workgroup 0 zeroes them (the aggregation runs after the launch)
     DevState* st;
     u64* tiles;          // look-back descriptors
     const Table* tab;    // device copy (the exotic-only replay's table after the exotic list grew)
@@ -297,7 +311,8 @@ __host__ __device__ inline u32 log_subregion(u64 key) {
 }
 
 // ---- launchers (fr_kernels.hip) --------------------------------------------------
-hipError_t launch_table_init(GSlot* slots, u64 n, hipStream_t s);
+// st != nullptr: workgroup 0 also writes the reset image of the device state (all zero, no error offset)
+hipError_t launch_table_init(GSlot* slots, u64 n, DevState* st, hipStream_t s);
 hipError_t launch_chunk_scan(const ScanArgs& a, int grid, hipStream_t s);
 int chunk_occupancy();  // tally workgroups per CU the kernel is built for
 hipError_t launch_reinsert_overflow(Table t, DevState* st, const Overflow* src, u64 n, hipStream_t s);
@@ -328,12 +343,17 @@ struct alignas(32) FinRow {  // one live slot on its way to its first-occurrence
 };
 hipError_t launch_fin_hist(const GSlot* slots, u64 nslots, const BinMap& m, u32* cnt, u32* arr, hipStream_t s);
 hipError_t launch_fin_scan(const u32* cnt, u32* base, u64 n, void* temp, size_t* temp_bytes, hipStream_t s);
+// also zeroes cnt[0, nbins] again (its last reader, the scan, is done: fr_finalize issues no memset) and
+// writes the scan's last entry, the live-slot count, to *fin_out (pinned host memory)
 hipError_t launch_fin_scatter(const GSlot* slots, u64 nslots, const BinMap& m, const u32* base, const u32* arr,
-                              FinRow* rows, hipStream_t s);
+                              FinRow* rows, u32* cnt, u64* fin_out, hipStream_t s);
 hipError_t launch_fin_rank(GSlot* slots, u64 nk, const BinMap& m, const u32* base, const FinRow* rows, u64* keys_o,
                            u64* counts_o, u64* first_o, bool set_uidx, hipStream_t s);
+// o.err_first heads this call's block of error word + rc sums; the launch also zeroes the zero_n words of the
+// block the next call will use (zero_next), and a workgroup that meets a code with an error sets *err_flag
+// (pinned host memory, zeroed by the caller): only then does the host fetch the exact error word
 hipError_t launch_classify(const u64* keys, const u64* counts, u64 n, SheetArgs sh, int nsubs, int rc,
-                           ClassOut o, const NbrMap& nm, hipStream_t s);
+                           ClassOut o, const NbrMap& nm, u64* zero_next, u32 zero_n, u64* err_flag, hipStream_t s);
 // neighbourhood codes of one sheet row: sum over d <= nsubs of C(L, d) 5^d (every query symbol)
 u64 nbr_codes_per_row(int L, int nsubs);
 // (re)build the maps of nm (already allocated and zeroed) for the sheet sh; canon = 3 x S value ids
@@ -354,8 +374,9 @@ hipError_t launch_partition_rows(const u64* keys, const u64* counts_in, const u6
 hipError_t launch_merge_rows(Table t, DevState* st, const u64* rows, u64 n, hipStream_t s);
 // aggregate the launch log into the table and empty it (stream-ordered; reads log_n and the region
 // cursors on the device)
+// mir != nullptr (a device feed's last launch): the last workgroup mirrors the state and *last_byte into it
 hipError_t launch_log_aggregate(Table t, DevState* st, const LogEntry* log, u32 rcap, LogEntry* sub, u32 scap,
-                                u32 file_tag, u64 file_offset, hipStream_t s);
+                                u32 file_tag, u64 file_offset, HostMirror* mir, const u8* last_byte, hipStream_t s);
 size_t log_aggregate_temp_bytes();
 hipError_t launch_synth(u8* out, u64 r0, u64 n, int R, u64 seed, const u8* idx1, const u8* idx2, int S, int L1,
                         int L2, hipStream_t s);

@@ -1710,6 +1710,9 @@ __global__ __launch_bounds__(WG, FR_OCC) void chunk_kernel(ScanArgs args) {
         sh.ncold = 0;
         sh.nexo = 0;
         sh.err_off = 0xFFFFFFFFu;
+        // a feed's fold statistics start at zero: nothing in this launch reads them, the aggregation
+        // that updates them runs after it (instead of a memset dispatch ahead of the launch)
+        if (a.zero_fold && blockIdx.x == 0) a.st->log_fold_max = a.st->log_fold_over = 0;
     }
 #if defined(FR_STAMPS) && FR_STAMPS == 3
     if (tid == 0 && blockIdx.x < TRACE_WGS) g_wg_trace[(a.par * TRACE_WGS + blockIdx.x) * 2] = __builtin_amdgcn_s_memrealtime();
@@ -1912,7 +1915,17 @@ hipError_t launch_chunk_scan(const ScanArgs& a, int grid, hipStream_t s) {
 // ------------------------------------------------------------------------------------
 // table maintenance
 // ------------------------------------------------------------------------------------
-__global__ void table_init_kernel(GSlot* slots, u64 n) {
+__global__ void table_init_kernel(GSlot* slots, u64 n, DevState* st) {
+    // fr_reset: the device state's reset image too (zero counters, no error offset), by workgroup 0 --
+    // no upload dispatch behind this kernel
+    if (st && blockIdx.x == 0) {
+        static_assert(sizeof(DevState) % sizeof(u32) == 0 && offsetof(DevState, err_nospace) % sizeof(u32) == 0,
+                      "DevState is written as 32-bit words");
+        constexpr u32 E = (u32)(offsetof(DevState, err_nospace) / sizeof(u32));
+        u32* w = (u32*)st;
+        for (u32 i = threadIdx.x; i < (u32)(sizeof(DevState) / sizeof(u32)); i += blockDim.x)
+            w[i] = (i == E || i == E + 1) ? 0xFFFFFFFFu : 0u;
+    }
     for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
         GSlot g;
         g.key = 0;
@@ -1924,9 +1937,9 @@ __global__ void table_init_kernel(GSlot* slots, u64 n) {
     }
 }
 
-hipError_t launch_table_init(GSlot* slots, u64 n, hipStream_t s) {
+hipError_t launch_table_init(GSlot* slots, u64 n, DevState* st, hipStream_t s) {
     const int grid = (int)std::min<u64>((n + 255) / 256, 8192);
-    hipLaunchKernelGGL(table_init_kernel, dim3(grid > 0 ? grid : 1), dim3(256), 0, s, slots, n);
+    hipLaunchKernelGGL(table_init_kernel, dim3(grid > 0 ? grid : 1), dim3(256), 0, s, slots, n, st);
     return hipGetLastError();
 }
 
@@ -2225,9 +2238,8 @@ __global__ __launch_bounds__(256) void log_split_kernel(Table t, DevState* st, c
 #endif
 constexpr int RED_WG = FR_RED_WG;
 constexpr int RED_FB = RED_WG >= 512 ? 4 : 8;  // distinct codes per thread per insert batch (4: <= 128 VGPRs, two workgroups per CU)
-__global__ __launch_bounds__(RED_WG) void log_reduce_kernel(Table t, DevState* st, const LogEntry* sub, u32 scap,
-                                                         u32 file_tag, u64 ord0) {
-    if (st->log_n == 0) return;
+__device__ __forceinline__ void log_reduce_fold(Table t, DevState* st, const LogEntry* sub, u32 scap, u32 file_tag,
+                                                u64 ord0) {
     __shared__ AggSlot ls[AGG_LNS];
     __shared__ u32 zone_bits[CLAIM_WORDS];
     __shared__ u16 occ[AGG_LNS];  // the occupied slots of ls, listed for the inserts
@@ -2340,28 +2352,62 @@ __global__ __launch_bounds__(RED_WG) void log_reduce_kernel(Table t, DevState* s
         made += insert_rows<FB, true>(t, st, key, cnt, ord, tag, v, cz);
     }
     add_created(st, made);
+}
+
+// mir: a device feed's last launch.  The grid's last workgroup mirrors the device state as this launch
+// leaves it, and the feed's last byte, into the pinned host block: the host synchronises the stream and
+// reads them there, without the copy dispatches (and the idle gaps around them) of a read-back.
+__global__ __launch_bounds__(RED_WG) void log_reduce_kernel(Table t, DevState* st, const LogEntry* sub, u32 scap,
+                                                         u32 file_tag, u64 ord0, HostMirror* mir,
+                                                         const u8* last_byte) {
+    const bool logged = st->log_n != 0;  // (uniform; nobody changes it before every workgroup has read it)
+    if (logged) log_reduce_fold(t, st, sub, scap, file_tag, ord0);
+    else if (!mir) return;
     // every workgroup has read log_n and its cursor (the split pass read the region cursors before
     // this launch): the last one empties the log
     if (last_block(&st->log_red_done)) {
-        for (int i = threadIdx.x; i < LOG_NR; i += RED_WG)
-            __hip_atomic_store(&st->log_rcur[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int i = threadIdx.x; i < LOG_NSUB; i += RED_WG)
-            __hip_atomic_store(&st->log_scur[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (threadIdx.x == 0) __hip_atomic_store(&st->log_n, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (logged) {
+            for (int i = threadIdx.x; i < LOG_NR; i += RED_WG)
+                __hip_atomic_store(&st->log_rcur[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int i = threadIdx.x; i < LOG_NSUB; i += RED_WG)
+                __hip_atomic_store(&st->log_scur[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (threadIdx.x == 0) __hip_atomic_store(&st->log_n, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        // the state's words up to the log cursors, and the fold statistics behind them: the cursors, log_n
+        // and log_red_done are zero after every aggregation (the host fills them in), so one wave's stores
+        // carry the mirror.  Agent-scope loads: the other workgroups updated the counters with memory-side
+        // atomics, ordered before this workgroup's turn by last_block's fences.
+        if (mir && threadIdx.x < 64) {
+            constexpr u32 HEAD = (u32)(offsetof(DevState, log_rcur) / sizeof(u32));
+            static_assert(offsetof(DevState, log_rcur) % sizeof(u32) == 0 && HEAD <= 64, "one wave mirrors the state's head");
+            const u32* src = (const u32*)st;
+            u32* dst = (u32*)&mir->st;
+            constexpr u32 LOGN = (u32)(offsetof(DevState, log_n) / sizeof(u32));  // (being zeroed above: not read)
+            if (threadIdx.x < HEAD)
+                dst[threadIdx.x] = (threadIdx.x == LOGN || threadIdx.x == LOGN + 1) ? 0u
+                                   : __hip_atomic_load(src + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (threadIdx.x == 0) {
+                mir->st.log_fold_max = __hip_atomic_load(&st->log_fold_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                mir->st.log_fold_over = __hip_atomic_load(&st->log_fold_over, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                mir->last_byte = last_byte ? (u32)*last_byte : 0u;
+            }
+            __threadfence_system();
+        }
     }
 }
 
 size_t log_aggregate_temp_bytes() { return 0; }
 
 hipError_t launch_log_aggregate(Table t, DevState* st, const LogEntry* log, u32 rcap, LogEntry* sub, u32 scap,
-                                u32 file_tag, u64 file_offset, hipStream_t s) {
+                                u32 file_tag, u64 file_offset, HostMirror* mir, const u8* last_byte, hipStream_t s) {
     // reads log_n on the device and returns at once when no commit logged (the usual case for
     // low-cardinality runs: only commits of at least ScanArgs::log_min pairs log)
     const u64 ord0 = ((u64)file_tag << ORD_SHIFT) | file_offset;
     if (!LOG_DIRECT)  // (direct logging: the commits wrote the sub-region parts)
         hipLaunchKernelGGL(log_split_kernel, dim3(LOG_NR * SPLIT_WGS), dim3(256), 0, s, t, st, log, rcap, sub, scap,
                            file_tag, ord0);
-    hipLaunchKernelGGL(log_reduce_kernel, dim3(LOG_NSUB), dim3(RED_WG), 0, s, t, st, sub, scap, file_tag, ord0);
+    hipLaunchKernelGGL(log_reduce_kernel, dim3(LOG_NSUB), dim3(RED_WG), 0, s, t, st, sub, scap, file_tag, ord0,
+                       mir, last_byte);
     return hipGetLastError();  // log_reduce_kernel's last block emptied the log
 }
 
@@ -2554,8 +2600,16 @@ __global__ __launch_bounds__(256) void fin_hist_kernel(const GSlot* slots, u64 n
 
 // each live slot's row {ordinal, key, count, slot} to its bin's run, one 32-B sector per row
 __global__ __launch_bounds__(256) void fin_scatter_kernel(const GSlot* slots, u64 n, BinMap m, const u32* base,
-                                                          const u32* arr, FinRow* rows) {
+                                                          const u32* arr, FinRow* rows, u32* cnt, u64* fin_out) {
     const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    // the bin counts' last reader (the scan) is done: zero them for the next fr_finalize, which then needs no
+    // memset dispatch (a lane per slot: one round wherever the table has more slots than bins); and the scan's
+    // last entry, the live-slot count fr_finalize checks, straight into pinned host memory
+    for (u64 j = i; j <= m.nbins; j += (u64)gridDim.x * blockDim.x) cnt[j] = 0;
+    if (i == 0 && fin_out) {
+        *fin_out = base[m.nbins];
+        __threadfence_system();
+    }
     if (i >= n) return;
     const u32 k = arr[i];
     if (k == 0xFFFFFFFFu) return;
@@ -2607,8 +2661,9 @@ hipError_t launch_fin_scan(const u32* cnt, u32* base, u64 n, void* temp, size_t*
 }
 
 hipError_t launch_fin_scatter(const GSlot* slots, u64 nslots, const BinMap& m, const u32* base, const u32* arr,
-                              FinRow* rows, hipStream_t s) {
-    hipLaunchKernelGGL(fin_scatter_kernel, dim3(lane_grid(nslots)), dim3(256), 0, s, slots, nslots, m, base, arr, rows);
+                              FinRow* rows, u32* cnt, u64* fin_out, hipStream_t s) {
+    hipLaunchKernelGGL(fin_scatter_kernel, dim3(lane_grid(nslots)), dim3(256), 0, s, slots, nslots, m, base, arr, rows,
+                       cnt, fin_out);
     return hipGetLastError();
 }
 
@@ -3056,8 +3111,12 @@ __device__ __forceinline__ void class_pair_nbr(const NbrMap& nm, int a1, int a2,
 template <typename W>
 __global__ __launch_bounds__(CLS_WG) void classify_kernel(const u64* keys, const u64* counts, u64 n, SheetArgs sh,
                                                           int nsubs, int rc, ClassOut o, NbrMap nm,
-                                                          int sheet_in_lds, int names_in_lds) {
+                                                          int sheet_in_lds, int names_in_lds, u64* zero_next,
+                                                          u32 zero_n, u64* err_flag) {
     extern __shared__ __attribute__((aligned(16))) u8 cls_lds[];
+    // the error word + rc sums of the next fr_classify (the other of two alternating blocks): zeroed here,
+    // so no call issues a memset dispatch for its own
+    for (u64 i = blockIdx.x * (u64)CLS_WG + threadIdx.x; i < zero_n; i += (u64)gridDim.x * CLS_WG) zero_next[i] = 0;
     unsigned long long* lf = (unsigned long long*)cls_lds;
     unsigned long long* lr = lf + (names_in_lds ? sh.n_names : 0);
     W* s1 = (W*)(lr + (names_in_lds ? sh.n_names : 0));
@@ -3078,6 +3137,7 @@ __global__ __launch_bounds__(CLS_WG) void classify_kernel(const u64* keys, const
     const W* S2 = sheet_in_lds ? s2 : (const W*)sh.i2;
     const W* S2rc = sheet_in_lds ? s2rc : (const W*)sh.i2rc;
 
+    bool any_err = false;
     // grid-stride: the per-name sums stay in LDS over many codes (one flush per workgroup: the
     // flush's atomics all land on the same 2 x names addresses)
     for (u64 u = blockIdx.x * (u64)CLS_WG + threadIdx.x; u < n; u += (u64)gridDim.x * CLS_WG) {
@@ -3161,6 +3221,7 @@ __global__ __launch_bounds__(CLS_WG) void classify_kernel(const u64* keys, const
             }
         }
         if (err) {
+            any_err = true;
             atomicMax((unsigned long long*)o.err_first, (unsigned long long)~u);  // = min u
             if (o.err_which) o.err_which[u] = err;
         } else if (o.err_which) {
@@ -3188,6 +3249,9 @@ __global__ __launch_bounds__(CLS_WG) void classify_kernel(const u64* keys, const
             }
         }
     }
+    // pinned host memory (every lane that met an error stores the same value to the one address, once, after
+    // its loop): the host reads the exact error word, kept by the atomicMax above, only when the flag is set
+    if (any_err) *err_flag = 1;
     if (rc && names_in_lds) {
         __syncthreads();
         for (int i = threadIdx.x; i < sh.n_names; i += CLS_WG) {
@@ -3198,8 +3262,8 @@ __global__ __launch_bounds__(CLS_WG) void classify_kernel(const u64* keys, const
 }
 
 hipError_t launch_classify(const u64* keys, const u64* counts, u64 n, SheetArgs sh, int nsubs, int rc, ClassOut o,
-                           const NbrMap& nm, hipStream_t s) {
-    if (!n) return hipSuccess;
+                           const NbrMap& nm, u64* zero_next, u32 zero_n, u64* err_flag, hipStream_t s) {
+    // (no codes: one workgroup still zeroes the next call's block)
     // u32 images when every sheet entry (and so every matching query) has <= 10 symbols
     const bool narrow = sh.S > 0 && sh.L1u >= 0 && sh.L1u <= 10 && sh.L2u >= 0 && sh.L2u <= 10;
     const size_t wb = narrow ? 4 : 8;
@@ -3210,14 +3274,14 @@ hipError_t launch_classify(const u64* keys, const u64* counts, u64 n, SheetArgs 
     // the scalar-load path (FR_CLS_SCALAR) reads the rows from HBM; only the name sums use LDS then
     const int sheet_in_lds = (!FR_CLS_SCALAR && nb + sheet_bytes <= CLS_LDS_BYTES) ? 1 : 0;
     const size_t lds = nb + (sheet_in_lds ? sheet_bytes : 0) + 16;
-    const u64 grid = std::min<u64>((n + CLS_WG - 1) / CLS_WG, 2048);
+    const u64 grid = std::max<u64>(1, std::min<u64>((n + CLS_WG - 1) / CLS_WG, 2048));
     const bool wide = !(narrow && (sheet_in_lds || FR_CLS_SCALAR));
     if (!wide)
         hipLaunchKernelGGL(classify_kernel<u32>, dim3((u32)grid), dim3(CLS_WG), lds, s, keys, counts, n, sh, nsubs, rc,
-                           o, nm, sheet_in_lds, names_in_lds);
+                           o, nm, sheet_in_lds, names_in_lds, zero_next, zero_n, err_flag);
     else
         hipLaunchKernelGGL(classify_kernel<u64>, dim3((u32)grid), dim3(CLS_WG), lds, s, keys, counts, n, sh, nsubs, rc,
-                           o, nm, sheet_in_lds, names_in_lds);
+                           o, nm, sheet_in_lds, names_in_lds, zero_next, zero_n, err_flag);
     return hipGetLastError();
 }
 
