@@ -140,6 +140,60 @@ __device__ __forceinline__ u32 gather16(u32 c0, u32 c1, u32 c2, u32 c3) {
     return (v | (u << 8)) >> K;
 }
 
+// The tally's classifier works on pairs of dwords (FR_CLS_PAIR 1, the product build).  FR_CLS_PAIR 0
+// keeps the one-dword loop over classify4_fast: scripts/build_exp.sh NAME "-DFR_CLS_PAIR=0" builds it
+// from the same tree for A/B runs.  Results do not depend on the switch.
+#ifndef FR_CLS_PAIR
+#define FR_CLS_PAIR 1
+#endif
+
+// classify4_fast's two lookups on two consecutive dwords, with two variants of the tables: variant A
+// (dword wa, bytes 0-3 of the pair) puts its class flags in the low nibble, variant B (dword wb, bytes
+// 4-7) the same classes four bits higher, and the two class words are ORed.  Byte i of the pair word:
+//   bit 0 line end of byte i          bit 4 line end of byte 4 + i
+//   bit 1 ':' of byte i               bit 5 ':' of byte 4 + i
+//   bit 3 ' ' of byte i               bit 7 ' ' of byte 4 + i
+//   bit 2 '\r' and bit 6 the sentinel, of either byte: only ever tested over the whole wave-tile.
+// A class then takes one mask and one v_dot4_u32_u8 per 8 bytes (gather16p), not per 4.
+// v_perm's selectors 8-11 return the sign bit of table bytes 1, 3, 5, 7, so no hi-table entry at an odd
+// index may carry bit 7, or bytes 0x40-0x5F would read 0xFF: '\n' and '\r' (index 1) and ':' (index 7)
+// cannot sit at bit 7 of variant B, ' ' (index 4) can.  Selectors 13-15 return 0xFF, so bytes 0x68-0x7F
+// get their lo-table entry as it is: the entries that carry a class also carry the sentinel, and a pair
+// word with the sentinel set (the ASCII bytes h j m p r u x z }, the same nine in both variants, as with
+// classify4_fast) sends the wave-tile to classify4.  Both index masks keep bit 7 of the byte (0x87, and
+// five bits of w >> 3), so a byte >= 0x80 selects 0xFF in both tables: its class word is 0xFF, sentinel
+// included, and the wave-tile goes to classify4 as well, with no OR chain over the raw bytes.  The flagged
+// set is those nine ASCII bytes and 0x80-0xFF; every other byte gets exactly its classes
+// (tests/test_classifier_pair_tables.py, all 256 bytes in both variants).
+constexpr u32 PAIR_CR = 0x04040404u, PAIR_SENTINEL = 0x40404040u;
+__device__ __forceinline__ u32 classify8_pair(u32 wa, u32 wb) {
+    const u32 lo_a = __builtin_amdgcn_perm(0x00004500u, 0x00430048u, wa & 0x87878787u);
+    const u32 hi_a = __builtin_amdgcn_perm(0x02000008u, 0x00000500u, (wa >> 3) & 0x1F1F1F1Fu);
+    const u32 lo_b = __builtin_amdgcn_perm(0x00005400u, 0x007000C0u, wb & 0x87878787u);
+    const u32 hi_b = __builtin_amdgcn_perm(0x20000080u, 0x00001400u, (wb >> 3) & 0x1F1F1F1Fu);
+    // (lo_a & hi_a) | b in one v_bitop3 (truth table 0xF0 & 0xCC | 0xAA): left to itself the compiler keeps
+    // the two halves apart and ORs them once more for the wave-tile test
+    return __builtin_amdgcn_bitop3_b32(lo_a, hi_a, lo_b & hi_b, 0xEAu);
+}
+
+// Class K (0 line end, 1 ':', 3 ' ') of 16 bytes (two pair words) -> a 16-bit mask scaled by 2^K.
+// Weights 1, 2, 4, 8 sum byte i's low-nibble flag to bit i and its high-nibble flag to bit 4 + i: 8 bytes
+// in natural order per dot4, no carry (each nibble sums to at most 15).
+template <int K>
+__device__ __forceinline__ u32 gather16p(u32 d0, u32 d1) {
+    constexpr u32 M = 0x11111111u << K;
+    const u32 v = __builtin_amdgcn_udot4(d0 & M, 0x08040201u, 0u, false);
+    const u32 u = __builtin_amdgcn_udot4(d1 & M, 0x08040201u, 0u, false);
+    return v | (u << 8);
+}
+
+// four gather16p quarters -> the segment's 64-bit bitmap; the 2^K scale is undone once per 32-bit half
+template <int K>
+__device__ __forceinline__ u64 join16p(const u32 (&g)[4]) {
+    const u32 lo = (g[0] >> K) | (g[1] << (16 - K)), hi = (g[2] >> K) | (g[3] << (16 - K));
+    return ((u64)hi << 32) | (u64)lo;
+}
+
 __device__ __forceinline__ u64 agent_load(const u64* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -707,7 +761,26 @@ __device__ __forceinline__ SegClass seg_classify_src(const ScanArgs& a, u32 t, c
     sc.hi = false;
     if (s0 < bl) {
         u32 eol16[4], sp16[4], col16[4];
-        u32 acc = 0, raw = 0;
+        u32 acc = 0;
+        auto join = [](const u32 (&g)[4]) {
+            return ((u64)(g[2] | (g[3] << 16)) << 32) | (u64)(g[0] | (g[1] << 16));
+        };
+#if FR_CLS_PAIR
+#pragma unroll
+        for (int qv = 0; qv < SEG / 16; ++qv) {  // class words live one quarter at a time
+            const uint4 v = src(qv);
+            const u32 d0 = classify8_pair(v.x, v.y), d1 = classify8_pair(v.z, v.w);
+            eol16[qv] = gather16p<0>(d0, d1);
+            col16[qv] = gather16p<1>(d0, d1);
+            sp16[qv] = gather16p<3>(d0, d1);
+            acc |= d0 | d1;
+        }
+        u64 eol = join16p<0>(eol16), sp = join16p<3>(sp16), col = join16p<1>(col16);
+        bool cr = (acc & PAIR_CR) != 0;
+        // a sentinel byte or a byte >= 0x80 (0xFF from both tables: the raw bytes need no test of their own)
+        const bool slow = (acc & PAIR_SENTINEL) != 0;
+#else
+        u32 raw = 0;
 #pragma unroll
         for (int qv = 0; qv < SEG / 16; ++qv) {  // class words live one quarter at a time
             const uint4 v = src(qv);
@@ -719,24 +792,24 @@ __device__ __forceinline__ SegClass seg_classify_src(const ScanArgs& a, u32 t, c
             acc |= c0 | c1 | c2 | c3;
             raw |= v.x | v.y | v.z | v.w;
         }
-        if (__ballot(((acc | raw) & 0x80808080u) != 0) != 0) {  // a wave-uniform SGPR value: a scalar branch
+        u64 eol = join(eol16), sp = join(sp16), col = join(col16);
+        bool cr = (acc & 0x02020202u) != 0;
+        const bool slow = ((acc | raw) & 0x80808080u) != 0;
+#endif
+        // bit 4 (byte >= 0x80) exists in classify4's class words only (in a pair word it is a line end)
+        u32 hib = 0;
+        if (__ballot(slow) != 0) {  // a wave-uniform SGPR value: a scalar branch
             // a byte >= 0x80 or a fast-table sentinel somewhere in the wave-tile: the exact classifier,
             // out of line on the segment re-read from L2 (no register of the common path is held for it)
             const Cls16 e = classes_exact(a, t, lane);
-#pragma unroll
-            for (int qv = 0; qv < SEG / 16; ++qv) {
-                eol16[qv] = e.eol[qv];
-                sp16[qv] = e.sp[qv];
-                col16[qv] = e.col[qv];
-            }
-            acc = e.acc;
+            eol = join(e.eol);
+            sp = join(e.sp);
+            col = join(e.col);
+            cr = (e.acc & 0x02020202u) != 0;
+            hib = e.acc & 0x10101010u;
         }
-        auto join = [](const u32 (&g)[4]) {
-            return ((u64)(g[2] | (g[3] << 16)) << 32) | (u64)(g[0] | (g[1] << 16));
-        };
-        u64 eol = join(eol16), sp = join(sp16), col = join(col16);
         u64 tm = eol;
-        if (__ballot((acc & 0x02020202u) != 0) != 0) {
+        if (__ballot(cr) != 0) {
             // '\r' somewhere in the wave (CRLF / CR files): a '\r' right before a '\n' ends no line.
             // The segment (and the byte after it) is re-read from L2 here, so no class word has to
             // stay live through the common path.
@@ -748,9 +821,9 @@ __device__ __forceinline__ SegClass seg_classify_src(const ScanArgs& a, u32 t, c
             for (int qv = 0; qv < SEG / 16; ++qv)
                 cr16[qv] = gather16<1>(classify4(q.v[qv].x), classify4(q.v[qv].y), classify4(q.v[qv].z),
                                        classify4(q.v[qv].w));
-            const u64 cr = join(cr16), nl = eol & ~cr;
+            const u64 crm = join(cr16), nl = eol & ~crm;
             const u64 nxt = (q.nx & 0xFFu) == (u32)'\n' ? 1ull : 0ull;
-            tm = eol & ~(cr & ((nl >> 1) | (nxt << 63)));
+            tm = eol & ~(crm & ((nl >> 1) | (nxt << 63)));
         }
         const u32 bvalid = bl - s0;
         if (bvalid < SEG) {
@@ -770,7 +843,7 @@ __device__ __forceinline__ SegClass seg_classify_src(const ScanArgs& a, u32 t, c
         sc.eol = eol;
         if (s0 < tlen) {
             sc.tmask = tm;
-            sc.hi = (acc & 0x10101010u) != 0;  // exact own-byte test in drain_rare (kind 4)
+            sc.hi = hib != 0;  // exact own-byte test in drain_rare (kind 4)
         }
     }
     sc.c = __popcll(sc.tmask);
