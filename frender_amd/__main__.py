@@ -64,6 +64,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="who compresses the outputs: gpu (default: the routed bytes are deflated on the GPU, "
                         "no larger than zlib level 9 makes them on FASTQ), libdeflate or zlib (host threads at "
                         "--gz-level)")
+    d.add_argument("--gz-format", choices=("gzip", "bgzf"), default="gzip",
+                   help="the outputs' framing: gzip (default: one member per destination per window) or bgzf "
+                        "(independent members of at most 64 KiB each and an EOF block, as bgzip writes: readable "
+                        "by bgzip/htslib tools, by this project's member-parallel readers and by scan "
+                        "--gz-reader gpu; 1.4-2.0 %% larger; needs --gz-writer gpu)")
     d.add_argument("--gpus", type=int, default=1,
                    help="GPUs (one process each; file pairs are dealt to them, rank 0 writes the outputs)")
     d.add_argument("--stage-times", action="store_true", help="print the demux's seconds per stage (stderr)")
@@ -88,6 +93,8 @@ def main(argv=None):
         frender_scan(args)
         return 0
     if getattr(args, "cmd", None) == "demux":
+        from .host import gz_format
+        gz_format(args)  # a bad writer/format pair ends here, before ranks start (frender_demux checks it too)
         if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
             # every rank must use the same output directory: the default names the minute
             child = (sys.argv[1:] if argv is None else list(argv))

@@ -155,11 +155,15 @@ _SIGS = {
     "fr_dmx_load_parts": (C.c_int, [P, C.c_int, P, P, C.c_int, C.POINTER(C.c_uint64)]),
     "fr_dmx_deflate": (C.c_int, [P, C.c_int, C.c_int, P, P]),
     "fr_dmx_fetch_deflated": (C.c_int, [P, C.c_int, P, C.c_uint64]),
+    "fr_dmx_deflate_bgzf": (C.c_int, [P, C.c_int, C.c_int, P]),
     "fr_defl_create": (P, [C.c_int]),
     "fr_defl_destroy": (None, [P]),
     "fr_defl_last_error": (C.c_char_p, [P]),
     "fr_defl_run": (C.c_int, [P, P, P, C.c_int, P, P]),
     "fr_defl_run_host": (C.c_int, [P, P, C.c_uint64, P, C.c_int, P, P]),
+    "fr_defl_run_bgzf": (C.c_int, [P, P, P, C.c_int, P]),
+    "fr_defl_run_bgzf_host": (C.c_int, [P, P, C.c_uint64, P, C.c_int, P]),
+    "fr_defl_kernel_ms": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fr_defl_out_bytes": (C.c_uint64, [P]),
     "fr_defl_stored_fallbacks": (C.c_uint64, [P]),
     "fr_defl_fetch": (C.c_int, [P, P, C.c_uint64]),
@@ -538,6 +542,15 @@ class Demux:
         self._ck(lib.fr_dmx_fetch_deflated(self.h, mate, _ptr(out), out.size), "fr_dmx_fetch_deflated")
         return comp, crc, out
 
+    def deflate_bgzf(self, mate: int, n_dest: int) -> tuple:
+        """The routed bytes of a mate as a run of complete BGZF members per destination
+        (fr_dmx_deflate_bgzf): (run bytes per destination, the runs concatenated)."""
+        comp = np.zeros(n_dest, np.uint64)
+        self._ck(lib.fr_dmx_deflate_bgzf(self.h, mate, n_dest, _ptr(comp)), "fr_dmx_deflate_bgzf")
+        out = np.empty(int(comp.sum()), np.uint8)
+        self._ck(lib.fr_dmx_fetch_deflated(self.h, mate, _ptr(out), out.size), "fr_dmx_fetch_deflated")
+        return comp, out
+
 
 class Deflater:
     """GPU deflate over byte ranges (fr_defl): see include/frender_amd.h."""
@@ -553,22 +566,38 @@ class Deflater:
             lib.fr_defl_destroy(self.h)
             self.h = None
 
-    def compress(self, data, offsets=None) -> tuple:
+    def compress(self, data, offsets=None, bgzf: bool = False) -> tuple:
         """Raw deflate streams of the ranges [offsets[s], offsets[s + 1]) of host bytes `data` (one
-        range when offsets is None): (stream bytes per range, CRC-32 per range, the streams)."""
+        range when offsets is None): (stream bytes per range, CRC-32 per range, the streams).  bgzf=True:
+        every range as a run of complete BGZF members instead (fr_defl_run_bgzf_host): (run bytes per
+        range, None, the runs)."""
         a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
         a = np.ascontiguousarray(a, dtype=np.uint8)
         offs = np.ascontiguousarray([0, a.size] if offsets is None else offsets, dtype=np.uint64)
         n = offs.size - 1
-        comp, crc = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
-        rc = lib.fr_defl_run_host(self.h, _ptr(a), a.size, _ptr(offs), n, _ptr(comp), _ptr(crc))
+        comp, crc = np.zeros(n, np.uint64), (None if bgzf else np.zeros(n, np.uint32))
+        if bgzf:
+            what = "fr_defl_run_bgzf_host"
+            rc = lib.fr_defl_run_bgzf_host(self.h, _ptr(a), a.size, _ptr(offs), n, _ptr(comp))
+        else:
+            what = "fr_defl_run_host"
+            rc = lib.fr_defl_run_host(self.h, _ptr(a), a.size, _ptr(offs), n, _ptr(comp), _ptr(crc))
         if rc != FR_OK:
-            raise FrenderError(f"fr_defl_run_host: {lib.fr_defl_last_error(self.h).decode()} (rc={rc})")
+            raise FrenderError(f"{what}: {lib.fr_defl_last_error(self.h).decode()} (rc={rc})")
         out = np.empty(int(lib.fr_defl_out_bytes(self.h)), np.uint8)
         rc = lib.fr_defl_fetch(self.h, _ptr(out), out.size)
         if rc != FR_OK:
             raise FrenderError(f"fr_defl_fetch: {lib.fr_defl_last_error(self.h).decode()} (rc={rc})")
         return comp, crc, out
+
+    def kernel_ms(self) -> tuple:
+        """The last run's kernel times by HIP events (fr_defl_kernel_ms): (block encoder, compaction or
+        framing), in ms."""
+        a, b = C.c_double(), C.c_double()
+        rc = lib.fr_defl_kernel_ms(self.h, C.byref(a), C.byref(b))
+        if rc != FR_OK:
+            raise FrenderError(f"fr_defl_kernel_ms: {lib.fr_defl_last_error(self.h).decode()} (rc={rc})")
+        return a.value, b.value
 
 
 class Inflater:
@@ -639,6 +668,10 @@ def gzip_frame(crc: int, isize: int) -> tuple:
     as Python's gzip writes them at level 9, mtime 0)."""
     import struct
     return b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x02\xff", struct.pack("<II", crc & 0xFFFFFFFF, isize & 0xFFFFFFFF)
+
+
+# the BGZF end-of-file marker (SAM specification, section 4.1.2): an empty member, once per file
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
 def _torch_stream_done(device: int):

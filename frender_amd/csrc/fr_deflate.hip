@@ -21,6 +21,12 @@
 //                 that would not shrink is stored instead
 // Then the block outputs are compacted (rocprim scan + copy) and the host folds the blocks' CRCs per
 // destination.  Bound: not HBM (a window is read ~3 times) but the matchfinder's dependent loads.
+//
+// BGZF mode (fr_defl_run_bgzf, demux --gz-format bgzf): the same kernel over other jobs.  A range is cut
+// every 65280 bytes into final blocks without history, so a block references nothing outside itself
+// (with hist = 0 a candidate's distance is at most the position's offset in the block, and a match's
+// length is cut at the block's end whatever lies in the bytes after it), and bgzf_frame writes each
+// block as a BGZF member of its own: header with BSIZE, the block, CRC-32 and ISIZE.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -436,6 +442,38 @@ __global__ void deflate_compact(const uint8_t* __restrict__ stage_out, const uin
     }
 }
 
+// BGZF mode's compaction (fr_defl_run_bgzf): block j's staged stream becomes a complete BGZF member at
+// boff[j] (the exclusive scan of out_len + BGZF_FRAME): the 18-byte gzip header whose extra field is the
+// BC subfield with BSIZE = the member's bytes - 1, the stream, then CRC-32 and ISIZE.  Members start at
+// any byte offset, so everything is copied and written byte by byte.
+constexpr uint32_t BGZF_CUT = 0xff00;   // input bytes per member (bgzip's block input)
+constexpr uint32_t BGZF_HEAD = 18, BGZF_FRAME = BGZF_HEAD + 8;
+constexpr uint32_t BGZF_MAX = 65536;    // BSIZE is 16 bits: a member's bytes - 1
+
+struct AddFrame {
+    __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v + BGZF_FRAME; }
+};
+
+__global__ void bgzf_frame(const uint8_t* __restrict__ stage_out, const uint32_t* __restrict__ out_len,
+                           const uint32_t* __restrict__ out_crc, const DJob* __restrict__ jobs,
+                           const uint64_t* __restrict__ boff, uint32_t n_jobs, uint8_t* __restrict__ out) {
+    for (uint32_t j = blockIdx.x; j < n_jobs; j += gridDim.x) {
+        const uint8_t* s = stage_out + (uint64_t)j * OUT_STRIDE;
+        uint8_t* d = out + boff[j];
+        const uint32_t n = out_len[j], t = threadIdx.x;
+        for (uint32_t i = t; i < n; i += blockDim.x) d[BGZF_HEAD + i] = s[i];
+        if (t < BGZF_FRAME) {
+            // 1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C', SLEN 2 | BSIZE | CRC32 | ISIZE
+            const uint64_t h0 = 0x0000000004088b1full, h1 = 0x000243420006ff00ull;
+            const uint32_t v = t < 16 ? (uint32_t)((t < 8 ? h0 : h1) >> (8 * (t & 7)))
+                               : t < 18 ? (n + BGZF_FRAME - 1) >> (8 * (t - 16))
+                               : t < 22 ? out_crc[j] >> (8 * (t - 18))
+                                        : jobs[j].len >> (8 * (t - 22));
+            d[t < BGZF_HEAD ? t : n + t] = (uint8_t)v;
+        }
+    }
+}
+
 // linear operator "feed n zero bytes into the raw CRC register", byte-sliced: 4 x 256 words
 void crc_shift_table(uint64_t n, uint32_t* T) {
     static uint32_t tab[256];
@@ -483,6 +521,8 @@ struct fr_defl {
     uint64_t c_jobs = 0, c_blen = 0, c_bcrc = 0, c_boff = 0, c_stage = 0, c_out = 0, c_tmp = 0, c_in = 0;
     uint64_t out_len = 0;
     uint64_t fallbacks = 0;  // blocks stored because their bit accounting did not add up (diagnostics)
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the last run's two kernels (fr_defl_kernel_ms)
+    bool timed = false;
     std::vector<DJob> hjobs;
     std::vector<uint32_t> hlen, hcrc;
     uint32_t shift64k[1024];
@@ -524,6 +564,8 @@ fr_defl* fr_defl_create_on(int device, hipStream_t stream) {
             return fail("fr_defl_create: stream");
         z->own_stream = true;
     }
+    for (hipEvent_t& e : z->ev)
+        if (hipEventCreate(&e) != hipSuccess) return fail("fr_defl_create: events");
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
     z->grid = 2 * cus;
@@ -548,34 +590,45 @@ void fr_defl_destroy(fr_defl* z) {
     void* p[] = {z->jobs, z->blen, z->bcrc, z->shift, z->boff, z->stage, z->out, z->scratch, z->in, z->tmp};
     for (void* x : p)
         if (x) (void)hipFree(x);
+    for (hipEvent_t e : z->ev)
+        if (e) (void)hipEventDestroy(e);
     if (z->own_stream && z->stream) (void)hipStreamDestroy(z->stream);
     delete z;
 }
 
 const char* fr_defl_last_error(const fr_defl* z) { return z ? z->err.c_str() : "null context"; }
 
-int fr_defl_run(fr_defl* z, const uint8_t* dev_data, const uint64_t* offsets, int n_streams, uint64_t* comp_bytes,
-                uint32_t* crc32_out) {
+}  // extern "C"
+
+// The streams [offsets[s], offsets[s + 1]) of dev_data, encoded and compacted on the device.  gzip mode
+// (bgzf false): a stream is cut every BLOCK bytes, a block references up to HIST bytes of its stream
+// before it, and the blocks of a stream concatenate into one raw deflate stream (crc32_out: its CRC-32).
+// BGZF mode: a stream is cut every BGZF_CUT bytes into final blocks without history, and bgzf_frame makes
+// each a member of its own (comp_bytes counts the framing; crc32_out is not used).
+static int defl_run(fr_defl* z, const uint8_t* dev_data, const uint64_t* offsets, int n_streams, uint64_t* comp_bytes,
+                    uint32_t* crc32_out, bool bgzf) {
     if (!z->scratch) return FR_ERR_HIP;
     if (n_streams < 0 || (n_streams && !offsets)) return z->err = "fr_defl_run: bad stream list", FR_ERR_INVALID;
     if (((uintptr_t)dev_data & 15u) != 0) return z->err = "fr_defl_run: data must be 16-byte aligned", FR_ERR_INVALID;
     DF(hipSetDevice(z->device));
+    const uint64_t cut = bgzf ? BGZF_CUT : BLOCK;
     z->hjobs.clear();
     for (int s = 0; s < n_streams; ++s) {
         const uint64_t a = offsets[s], b = offsets[s + 1];
         if (b < a) return z->err = "fr_defl_run: offsets must not decrease", FR_ERR_INVALID;
-        for (uint64_t x = a; x < b; x += BLOCK) {
+        for (uint64_t x = a; x < b; x += cut) {
             DJob j{};
             j.start = x;
-            j.len = (uint32_t)std::min<uint64_t>(BLOCK, b - x);
-            j.hist = (uint32_t)std::min<uint64_t>(HIST, x - a);
-            j.last = x + BLOCK >= b;
+            j.len = (uint32_t)std::min<uint64_t>(cut, b - x);
+            j.hist = bgzf ? 0u : (uint32_t)std::min<uint64_t>(HIST, x - a);
+            j.last = bgzf || x + cut >= b;
             z->hjobs.push_back(j);
         }
     }
     const uint64_t nj = z->hjobs.size();
     if (nj >= 0xFFFFFFFFull) return z->err = "fr_defl_run: too many blocks", FR_ERR_CAPACITY;
     z->out_len = 0;
+    z->timed = false;
     if (nj) {
         DF(grow(&z->jobs, z->c_jobs, nj));
         DF(grow(&z->blen, z->c_blen, nj + 1));  // grow-only: a window's buffers serve the next ones
@@ -585,9 +638,11 @@ int fr_defl_run(fr_defl* z, const uint8_t* dev_data, const uint64_t* offsets, in
         DF(hipMemcpyAsync(z->jobs, z->hjobs.data(), nj * sizeof(DJob), hipMemcpyHostToDevice, z->stream));
         DF(hipMemsetAsync(z->bcrc + nj, 0, 4, z->stream));  // the kernel counts its stored fallbacks here
         const uint32_t g = (uint32_t)std::min<uint64_t>(nj, (uint64_t)z->grid);
+        DF(hipEventRecord(z->ev[0], z->stream));
         hipLaunchKernelGGL(deflate_blocks, dim3(g), dim3(TPB), 0, z->stream, dev_data, z->jobs, (uint32_t)nj, z->stage,
                            z->blen, z->bcrc, z->scratch, z->shift);
         DF(hipGetLastError());
+        DF(hipEventRecord(z->ev[1], z->stream));
 #ifdef FRD_PROF
         {
             unsigned long long pr[12];
@@ -601,11 +656,20 @@ int fr_defl_run(fr_defl* z, const uint8_t* dev_data, const uint64_t* offsets, in
 #endif
         DF(hipMemsetAsync(z->blen + nj, 0, 4, z->stream));
         size_t tb = 0;
-        DF(rocprim::exclusive_scan(nullptr, tb, z->blen, z->boff, (uint64_t)0, (size_t)nj + 1,
-                                   rocprim::plus<uint64_t>(), z->stream));
-        DF(grow((uint8_t**)&z->tmp, z->c_tmp, tb + 1));
-        DF(rocprim::exclusive_scan(z->tmp, tb, z->blen, z->boff, (uint64_t)0, (size_t)nj + 1,
-                                   rocprim::plus<uint64_t>(), z->stream));
+        if (bgzf) {  // member offsets: every block's bytes and its frame
+            const auto framed = rocprim::make_transform_iterator(z->blen, AddFrame{});
+            DF(rocprim::exclusive_scan(nullptr, tb, framed, z->boff, (uint64_t)0, (size_t)nj + 1,
+                                       rocprim::plus<uint64_t>(), z->stream));
+            DF(grow((uint8_t**)&z->tmp, z->c_tmp, tb + 1));
+            DF(rocprim::exclusive_scan(z->tmp, tb, framed, z->boff, (uint64_t)0, (size_t)nj + 1,
+                                       rocprim::plus<uint64_t>(), z->stream));
+        } else {
+            DF(rocprim::exclusive_scan(nullptr, tb, z->blen, z->boff, (uint64_t)0, (size_t)nj + 1,
+                                       rocprim::plus<uint64_t>(), z->stream));
+            DF(grow((uint8_t**)&z->tmp, z->c_tmp, tb + 1));
+            DF(rocprim::exclusive_scan(z->tmp, tb, z->blen, z->boff, (uint64_t)0, (size_t)nj + 1,
+                                       rocprim::plus<uint64_t>(), z->stream));
+        }
         z->hlen.resize(nj);
         z->hcrc.resize(nj);
         DF(hipMemcpyAsync(z->hlen.data(), z->blen, nj * 4, hipMemcpyDeviceToHost, z->stream));
@@ -616,39 +680,87 @@ int fr_defl_run(fr_defl* z, const uint8_t* dev_data, const uint64_t* offsets, in
         uint64_t total = 0;
         for (uint64_t k = 0; k < nj; ++k) {
             if (z->hlen[k] > OUT_STRIDE) return z->err = "fr_defl_run: a block's bit accounting failed", FR_ERR_DEVICE;
-            total += z->hlen[k];
+            // (a stored member of BGZF_CUT bytes is 65311 bytes: this is a broken block, never written)
+            if (bgzf && z->hlen[k] + BGZF_FRAME > BGZF_MAX)
+                return z->err = "fr_defl_run_bgzf: a member would exceed 65536 bytes", FR_ERR_DEVICE;
+            total += z->hlen[k] + (bgzf ? BGZF_FRAME : 0u);
         }
         DF(grow(&z->out, z->c_out, total + 16));
-        hipLaunchKernelGGL(deflate_compact, dim3((uint32_t)std::min<uint64_t>(nj, 4096)), dim3(256), 0, z->stream,
-                           z->stage, z->blen, z->boff, (uint32_t)nj, z->out);
+        const dim3 cg((uint32_t)std::min<uint64_t>(nj, 4096));
+        DF(hipEventRecord(z->ev[2], z->stream));
+        if (bgzf)
+            hipLaunchKernelGGL(bgzf_frame, cg, dim3(256), 0, z->stream, z->stage, z->blen, z->bcrc, z->jobs, z->boff,
+                               (uint32_t)nj, z->out);
+        else
+            hipLaunchKernelGGL(deflate_compact, cg, dim3(256), 0, z->stream, z->stage, z->blen, z->boff, (uint32_t)nj,
+                               z->out);
         DF(hipGetLastError());
+        DF(hipEventRecord(z->ev[3], z->stream));
         DF(hipStreamSynchronize(z->stream));
         z->out_len = total;
+        z->timed = true;
     }
     uint64_t k = 0;
     for (int s = 0; s < n_streams; ++s) {
         const uint64_t a = offsets[s], b = offsets[s + 1];
         uint64_t bytes = 0;
         uint32_t crc = 0;
-        for (uint64_t x = a; x < b; x += BLOCK, ++k) {
-            const uint64_t n = std::min<uint64_t>(BLOCK, b - x);
-            crc = (n == BLOCK ? crc_apply(z->shift64k, crc) : (uint32_t)crc32_combine(crc, 0, (z_off_t)n)) ^ z->hcrc[k];
-            bytes += z->hlen[k];
+        for (uint64_t x = a; x < b; x += cut, ++k) {
+            const uint64_t n = std::min<uint64_t>(cut, b - x);
+            if (!bgzf)
+                crc = (n == BLOCK ? crc_apply(z->shift64k, crc) : (uint32_t)crc32_combine(crc, 0, (z_off_t)n)) ^ z->hcrc[k];
+            bytes += z->hlen[k] + (bgzf ? BGZF_FRAME : 0u);
         }
         comp_bytes[s] = bytes;
-        crc32_out[s] = crc;
+        if (!bgzf) crc32_out[s] = crc;
     }
     return FR_OK;
 }
 
-int fr_defl_run_host(fr_defl* z, const uint8_t* data, uint64_t len, const uint64_t* offsets, int n_streams,
-                     uint64_t* comp_bytes, uint32_t* crc32_out) {
+// the host buffer on the device, with the 16 readable bytes past its end
+static int defl_upload(fr_defl* z, const uint8_t* data, uint64_t len) {
     if (!z->scratch) return FR_ERR_HIP;
     DF(hipSetDevice(z->device));
     DF(grow(&z->in, z->c_in, len + 16));
     if (len) DF(hipMemcpyAsync(z->in, data, len, hipMemcpyHostToDevice, z->stream));
     DF(hipMemsetAsync(z->in + len, 0, 16, z->stream));
-    return fr_defl_run(z, z->in, offsets, n_streams, comp_bytes, crc32_out);
+    return FR_OK;
+}
+
+extern "C" {
+
+int fr_defl_run(fr_defl* z, const uint8_t* dev_data, const uint64_t* offsets, int n_streams, uint64_t* comp_bytes,
+                uint32_t* crc32_out) {
+    return defl_run(z, dev_data, offsets, n_streams, comp_bytes, crc32_out, false);
+}
+
+int fr_defl_run_bgzf(fr_defl* z, const uint8_t* dev_data, const uint64_t* offsets, int n_streams,
+                     uint64_t* comp_bytes) {
+    return defl_run(z, dev_data, offsets, n_streams, comp_bytes, nullptr, true);
+}
+
+int fr_defl_run_host(fr_defl* z, const uint8_t* data, uint64_t len, const uint64_t* offsets, int n_streams,
+                     uint64_t* comp_bytes, uint32_t* crc32_out) {
+    const int rc = defl_upload(z, data, len);
+    return rc != FR_OK ? rc : fr_defl_run(z, z->in, offsets, n_streams, comp_bytes, crc32_out);
+}
+
+int fr_defl_run_bgzf_host(fr_defl* z, const uint8_t* data, uint64_t len, const uint64_t* offsets, int n_streams,
+                          uint64_t* comp_bytes) {
+    const int rc = defl_upload(z, data, len);
+    return rc != FR_OK ? rc : fr_defl_run_bgzf(z, z->in, offsets, n_streams, comp_bytes);
+}
+
+int fr_defl_kernel_ms(fr_defl* z, double* encode_ms, double* pack_ms) {
+    float a = 0, b = 0;
+    if (z->timed) {  // the run synchronised its stream
+        DF(hipSetDevice(z->device));
+        DF(hipEventElapsedTime(&a, z->ev[0], z->ev[1]));
+        DF(hipEventElapsedTime(&b, z->ev[2], z->ev[3]));
+    }
+    if (encode_ms) *encode_ms = a;
+    if (pack_ms) *pack_ms = b;
+    return FR_OK;
 }
 
 uint64_t fr_defl_out_bytes(const fr_defl* z) { return z ? z->out_len : 0; }

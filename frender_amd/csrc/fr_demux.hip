@@ -635,7 +635,8 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     return FR_OK;
 }
 
-int fr_dmx_deflate(fr_dmx* d, int mate, int n_dest, uint64_t* comp_bytes, uint32_t* crc32) {
+// the routed bytes of a mate through its fr_defl: gzip streams (crc32 set) or BGZF member runs
+static int dmx_deflate(fr_dmx* d, int mate, int n_dest, uint64_t* comp_bytes, uint32_t* crc32, bool bgzf) {
     if (mate < 0 || mate > 1) return d->err = "mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
     if (n_dest < 0 || (u64)n_dest + 1 != d->hoff[mate].size())
         return d->err = "fr_dmx_deflate: n_dest differs from the last fr_dmx_route", FR_ERR_INVALID;
@@ -645,9 +646,18 @@ int fr_dmx_deflate(fr_dmx* d, int mate, int n_dest, uint64_t* comp_bytes, uint32
         const char* e = fr_defl_last_error(d->defl[mate]);
         if (e && *e) return d->err = std::string("fr_dmx_deflate: ") + e, FR_ERR_HIP;
     }
-    const int rc = fr_defl_run(d->defl[mate], d->out[mate], d->hoff[mate].data(), n_dest, comp_bytes, crc32);
+    const int rc = bgzf ? fr_defl_run_bgzf(d->defl[mate], d->out[mate], d->hoff[mate].data(), n_dest, comp_bytes)
+                        : fr_defl_run(d->defl[mate], d->out[mate], d->hoff[mate].data(), n_dest, comp_bytes, crc32);
     if (rc != FR_OK) d->err = std::string("fr_dmx_deflate: ") + fr_defl_last_error(d->defl[mate]);
     return rc;
+}
+
+int fr_dmx_deflate(fr_dmx* d, int mate, int n_dest, uint64_t* comp_bytes, uint32_t* crc32) {
+    return dmx_deflate(d, mate, n_dest, comp_bytes, crc32, false);
+}
+
+int fr_dmx_deflate_bgzf(fr_dmx* d, int mate, int n_dest, uint64_t* comp_bytes) {
+    return dmx_deflate(d, mate, n_dest, comp_bytes, nullptr, true);
 }
 
 int fr_dmx_fetch_deflated(fr_dmx* d, int mate, uint8_t* out, uint64_t len) {

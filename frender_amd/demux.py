@@ -24,7 +24,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import parse_files
+from .host import gz_format, parse_files
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
 # the column order `scan` itself writes (frender.py:482-501, report_analysis)
@@ -154,6 +154,31 @@ class _GzDevice:
         self.f.close()
 
 
+class _BgzfDevice:
+    """A .fq.gz writer of BGZF members the GPU made, framing included (fr_dmx_deflate_bgzf): a window's run
+    of members is appended as it is, and close() ends the file with the BGZF EOF block, once.  A file
+    nothing was written to is the EOF block alone: an empty gzip file and an empty BGZF file."""
+    eof = True
+
+    def __init__(self, path: str, level: int):
+        self.f = open(path, "wb")
+        self.level = level
+
+    def write_members(self, arr: np.ndarray, start: int, end: int) -> None:
+        if end > start:
+            self.f.write(memoryview(arr)[start:end])
+
+    def close(self) -> None:
+        if self.eof:
+            self.f.write(_lib.BGZF_EOF)
+        self.f.close()
+
+
+class _BgzfPart(_BgzfDevice):
+    """One pair's part of a BGZF output (demux --gpus N): no EOF block, rank 0 ends the joined file."""
+    eof = False
+
+
 class _GzFile:
     """gzip.open writer with the same write_from interface (the image has no libdeflate)."""
 
@@ -176,10 +201,14 @@ def out_path(name, out_dir, infix, read) -> str:
 
 
 _WRITERS = {"gpu": _GzDevice, "libdeflate": _GzMembers, "zlib": _GzFile}
+_DEVICE_WRITERS = (_GzDevice, _BgzfDevice)  # the GPU compresses: the host's cores are free to inflate
 
 
-def writer_kind(name: str):
-    """The writer class of --gz-writer (libdeflate falls back to zlib where the image has none)."""
+def writer_kind(name: str, fmt: str = "gzip"):
+    """The writer class of --gz-writer and --gz-format (libdeflate falls back to zlib where the image has
+    none)."""
+    if fmt == "bgzf":
+        return _BgzfDevice
     if name == "libdeflate" and _LD is None:
         name = "zlib"
     return _WRITERS[name]
@@ -355,7 +384,21 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 if val == _lib.FR_DMX_MISSING:
                     raise SystemExit(f"Couldn't find barcode {code} in supplied frender result file!")
                 raise SystemExit("Unrecognized read type found in supplied frender result file!")
-            if isinstance(writers[0]["R1"], _GzDevice):  # the GPU deflates every destination's bytes
+            if isinstance(writers[0]["R1"], _BgzfDevice):  # the GPU makes every destination's BGZF members
+                z1, o1 = dmx.deflate_bgzf(0, len(writers))
+                z2, o2 = dmx.deflate_bgzf(1, len(writers))
+                t4 = clock()
+                for j in pending:
+                    j.result()
+                c1 = np.concatenate([[0], np.cumsum(z1)]).astype(np.int64)
+                c2 = np.concatenate([[0], np.cumsum(z2)]).astype(np.int64)
+                pending = []
+                for k, w in enumerate(writers):
+                    if b1[k]:
+                        pending.append(pool.submit(w["R1"].write_members, o1, int(c1[k]), int(c1[k + 1])))
+                    if b2[k]:
+                        pending.append(pool.submit(w["R2"].write_members, o2, int(c2[k]), int(c2[k + 1])))
+            elif isinstance(writers[0]["R1"], _GzDevice):  # the GPU deflates every destination's bytes
                 z1, k1, o1 = dmx.deflate(0, len(writers))
                 z2, k2, o2 = dmx.deflate(1, len(writers))
                 t4 = clock()
@@ -407,13 +450,14 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
 def frender_demux(args, dev=None) -> None:
     """frender.py:733-814 with the per-record loop on the GPU."""
     t_start = time.perf_counter()
+    fmt = gz_format(args)
     index_hop = not args.no_index_hop
     ambiguous = not args.no_ambiguous
     undeter = not args.no_undeter
     samples = not args.no_samples
     level = getattr(args, "gz_level", None) or 9  # gzip.open's default, as the reference writes
-    kind = writer_kind(getattr(args, "gz_writer", None) or "gpu")
-    if kind is _GzDevice and getattr(args, "gz_level", None) not in (None, 9):
+    kind = writer_kind(getattr(args, "gz_writer", None) or "gpu", fmt)
+    if kind in _DEVICE_WRITERS and getattr(args, "gz_level", None) not in (None, 9):
         print(f"Warning: --gz-level {args.gz_level} has no effect with --gz-writer gpu (the GPU writer's streams "
               "are no larger than level 9's); use --gz-writer libdeflate or zlib for another level", file=sys.stderr)
     infix = args.o
@@ -522,7 +566,7 @@ def frender_demux(args, dev=None) -> None:
 # must be read in lockstep), writes each pair's destinations into part files of its own, and rank 0
 # concatenates the parts in pair order into the final files.  The writers emit gzip members, so a
 # concatenation is a valid gzip stream whose text is the concatenation of the pairs' texts: the
-# reference's file content.  The first failing pair (in pair order) decides the error, raised by the
+# reference's file content.  (BGZF parts are written without the EOF block; rank 0 appends the one.)  The first failing pair (in pair order) decides the error, raised by the
 # rank that met it, after rank 0 has written the pairs up to it.
 
 def _inflate_threads(kind) -> int:
@@ -530,7 +574,7 @@ def _inflate_threads(kind) -> int:
     process's CPUs up to 16.  The pool inflates as many files at once as fit its block budget (4 of
     the config-5 shape's 443-MB mates: this pair's and the next), each big single-member file split
     over its share of the threads."""
-    if kind is not _GzDevice:
+    if kind not in _DEVICE_WRITERS:
         return 4
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)
     return max(4, min(16, n))
@@ -585,7 +629,7 @@ def _demux_ranks(group, args, dev, pairs, results, route_of, keys, vals, names, 
         for j, k in enumerate(mine):
             d = os.path.join(parts, str(k))
             os.makedirs(d, exist_ok=True)
-            writers = [open_files(n, d, infix, level, kind) for n in names]
+            writers = [open_files(n, d, infix, level, _BgzfPart if kind is _BgzfDevice else kind) for n in names]
             try:
                 _demux_pair(dmx, pool, gz, 2 * j, 2 * j + 1, pairs[k][0], pairs[k][1], results, route_of, writers,
                             window)
@@ -620,7 +664,9 @@ def _demux_ranks(group, args, dev, pairs, results, route_of, keys, vals, names, 
                         if os.path.exists(part):
                             with open(part, "rb") as f:
                                 shutil.copyfileobj(f, out, 16 << 20)
-                    if out.tell() == 0:  # no pair reached it: an empty gzip file, as the reference's writer
+                    if kind is _BgzfDevice:  # the parts carry no EOF block: the file's one (alone if no pair reached it)
+                        out.write(_lib.BGZF_EOF)
+                    elif out.tell() == 0:  # no pair reached it: an empty gzip file, as the reference's writer
                         out.write(gzip.compress(b"", compresslevel=level))
     reduce_min(group, _wire(group), [0])  # the parts are read: remove them
     if rank == 0:

@@ -113,3 +113,16 @@ def parse_files(file_dict: dict, just_r1: bool) -> list:
 def reverse_complement(s: str) -> str:
     """frender.py:210-211."""
     return s.translate(str.maketrans("ATGCNatgcn", "TACGNtacgn"))[::-1]
+
+
+def gz_format(args) -> str:
+    """--gz-format of a demux's arguments (a namespace without it means gzip), checked against --gz-writer:
+    only the GPU writer makes BGZF.  Called before anything is opened or created."""
+    fmt = getattr(args, "gz_format", None) or "gzip"
+    if fmt not in ("gzip", "bgzf"):
+        raise SystemExit(f"--gz-format {fmt}: expected gzip or bgzf")
+    writer = getattr(args, "gz_writer", None) or "gpu"
+    if fmt == "bgzf" and writer != "gpu":
+        raise SystemExit(f"--gz-format bgzf needs --gz-writer gpu (got {writer}): the host writers make plain gzip "
+                         "members only")
+    return fmt

@@ -359,6 +359,11 @@ int fr_dmx_fetch(fr_dmx* d, int mate, uint8_t* out, uint64_t len);
  * them). */
 int fr_dmx_deflate(fr_dmx* d, int mate, int n_dest, uint64_t* comp_bytes, uint32_t* crc32);
 int fr_dmx_fetch_deflated(fr_dmx* d, int mate, uint8_t* out, uint64_t len);
+/* the same bytes as BGZF (fr_defl_run_bgzf): every destination that has bytes becomes a run of complete
+ * BGZF members, comp_bytes[k] = the run's byte count with its framing (0: no bytes routed).  The runs are
+ * fetched with fr_dmx_fetch_deflated and appended to the destination's file as they are; the file's one
+ * EOF block is the host's to write. */
+int fr_dmx_deflate_bgzf(fr_dmx* d, int mate, int n_dest, uint64_t* comp_bytes);
 
 /* ---- GPU deflate over any byte ranges (fr_deflate.hip; fr_dmx_deflate runs it on the routed bytes).
  * Stream s is bytes [offsets[s], offsets[s + 1]) of the device buffer dev_data (4-byte aligned, 16
@@ -374,7 +379,21 @@ int fr_defl_run(fr_defl* z, const uint8_t* dev_data, const uint64_t* offsets, in
 /* the same over a host buffer (copied to the device first) */
 int fr_defl_run_host(fr_defl* z, const uint8_t* data, uint64_t len, const uint64_t* offsets, int n_streams,
                      uint64_t* comp_bytes, uint32_t* crc32);
-/* the last run's streams, concatenated in stream order */
+/* BGZF mode: every stream becomes a run of complete BGZF members (the SAM specification's section 4.1: gzip
+ * members whose extra field carries their size, so that a reader finds and inflates them independently).  A
+ * stream is cut every 65280 bytes (bgzip's block input); each slice is one final deflate block that
+ * references nothing before it, framed by the 18-byte header with BSIZE and the CRC32 / ISIZE trailer.
+ * comp_bytes[s] = the run's byte count with its framing, 0 for an empty stream.  No EOF block is produced:
+ * the writer of a file appends it once.  A member that would exceed 65536 bytes is never written
+ * (FR_ERR_DEVICE; a stored slice makes 65311). */
+int fr_defl_run_bgzf(fr_defl* z, const uint8_t* dev_data, const uint64_t* offsets, int n_streams,
+                     uint64_t* comp_bytes);
+int fr_defl_run_bgzf_host(fr_defl* z, const uint8_t* data, uint64_t len, const uint64_t* offsets, int n_streams,
+                          uint64_t* comp_bytes);
+/* the last run's kernel times by HIP events (0 when it had no bytes): the block encoder, and the kernel
+ * that packs the blocks' outputs (gzip mode's compaction, BGZF mode's framing) */
+int fr_defl_kernel_ms(fr_defl* z, double* encode_ms, double* pack_ms);
+/* the last run's streams (BGZF mode: member runs), concatenated in stream order */
 uint64_t fr_defl_out_bytes(const fr_defl* z);
 /* blocks this context stored because their dynamic encoding's bit accounting did not add up (the stored
  * form is always a valid encoding of the block; a nonzero count is a diagnostic, not an error) */
