@@ -41,7 +41,8 @@ def build_parser() -> argparse.ArgumentParser:
                         "the host pool; single GPU)")
     p.add_argument("files", nargs="+", help="Fastq file(s) or a directory of fastq files")
     p.set_defaults(cmd="scan")
-    d = sub.add_parser("demux", help="Demultiplex paired fastq files using a frender scan result file")
+    d = sub.add_parser("demux", help="Demultiplex paired fastq files using a frender scan result file (-r) or the "
+                                        "sample sheet itself (-b with -n)")
     d.add_argument("-i", "--no-index-hop", action="store_true",
                    help="don't split index hop reads into their own file (will be included in undetermined file "
                         "unless -u is set)")
@@ -54,7 +55,17 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("-d", metavar="output_dir",
                    default=f"./frender-demux-output_{datetime.strftime(datetime.now(timezone.utc), '%Y-%M-%d_%H%M_%Z')}/",
                    help="output directory (default: ./frender-demux-output_{date_time}/)")
-    d.add_argument("-r", metavar="result_file", required=True, help="REQUIRED: frender scan result file")
+    d.add_argument("-r", metavar="result_file",
+                   help="frender scan result file (one of -r and -b is REQUIRED)")
+    d.add_argument("-b", metavar="barcode_table",
+                   help=".csv barcode association table: demultiplex straight from the sample sheet in one pass, "
+                        "every read classified as `scan -n N -b` classifies its code (needs -n; no scan, no "
+                        "result file).  There is no -rc here: the reference's -rc call depends on per-sample read "
+                        "counts over the whole run; supply the sheet with index 2 in the reads' orientation, or "
+                        "use scan -rc and demux -r")
+    d.add_argument("-n", metavar="[int]", type=int,
+                   help="with -b (required there, rejected with -r): number of mismatches allowed between the "
+                        "sheet's barcodes and the reads', as scan's -n")
     d.add_argument("--strict-header", action="store_true",
                    help="reject a results file in scan's own column order, as frender.py does (default: accept it)")
     d.add_argument("--gz-level", type=int, default=None,
@@ -93,7 +104,11 @@ def main(argv=None):
         frender_scan(args)
         return 0
     if getattr(args, "cmd", None) == "demux":
-        from .host import gz_format
+        from .host import demux_mode, gz_format
+        try:
+            demux_mode(args)  # -r or -b with -n, before ranks start (frender_demux checks it too)
+        except SystemExit as e:
+            parser.error(str(e))
         gz_format(args)  # a bad writer/format pair ends here, before ranks start (frender_demux checks it too)
         if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
             # every rank must use the same output directory: the default names the minute

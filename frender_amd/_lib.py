@@ -145,6 +145,7 @@ _SIGS = {
     "fr_dmx_destroy": (None, [P]),
     "fr_dmx_last_error": (C.c_char_p, [P]),
     "fr_dmx_set_table": (C.c_int, [P, P, P, C.c_uint64]),
+    "fr_dmx_set_sheet": (C.c_int, [P, P, C.c_int, P, C.c_int, P]),
     "fr_dmx_load": (C.c_int, [P, C.c_int, P, C.c_uint64, u64p]),
     "fr_dmx_load_device": (C.c_int, [P, C.c_int, P, C.c_uint64, u64p]),
     "fr_dmx_records": (C.c_int, [P, C.c_int, P, C.c_uint64, P, P]),
@@ -261,6 +262,7 @@ def pack_lower(s: str) -> int:
 
 
 FR_DMX_MISSING, FR_DMX_BADTYPE, FR_DMX_EXOTIC = -1, -2, -3
+FR_DMX_LEN1, FR_DMX_LEN2, FR_DMX_NOPLUS = -4, -5, -6  # sheet mode: scan's error 1, 2, 3 for the code
 
 
 _PACK_LUT = np.zeros(128, dtype=np.uint8)
@@ -477,11 +479,24 @@ class Demux:
         if self.h:
             lib.fr_dmx_destroy(self.h)
             self.h = None
+            self._sheet_ctx = None
 
     def set_table(self, keys: np.ndarray, vals: np.ndarray):
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         vals = np.ascontiguousarray(vals, dtype=np.int32)
         self._ck(lib.fr_dmx_set_table(self.h, _ptr(keys), _ptr(vals), keys.size), "fr_dmx_set_table")
+        self._sheet_ctx = None
+
+    def set_sheet(self, ctx: "Context", num_subs: int, row_dest, class_dest):
+        """Sheet mode (fr_dmx_set_sheet): classify every R2 code against ctx's sheet (ctx.set_sheet first) with
+        num_subs; row_dest[row] takes a demuxable code, class_dest[class] the others.  ctx stays referenced
+        here, and must keep its sheet, until the next set_table / set_sheet / close."""
+        rd = np.ascontiguousarray(row_dest, dtype=np.int32)
+        cd = np.ascontiguousarray(class_dest, dtype=np.int32)
+        if cd.size != 4:
+            raise ValueError("class_dest: one destination per class (4)")
+        self._ck(lib.fr_dmx_set_sheet(self.h, ctx.h, int(num_subs), _ptr(rd), rd.size, _ptr(cd)), "fr_dmx_set_sheet")
+        self._sheet_ctx = ctx
 
     def load(self, mate: int, data) -> int:
         a = np.frombuffer(data, dtype=np.uint8)

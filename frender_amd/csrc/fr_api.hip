@@ -1909,3 +1909,16 @@ int fr_synth_device(fr_ctx* ctx, uint8_t* dev_out, uint64_t r0, uint64_t n, int 
 }
 
 }  // extern "C"
+
+namespace fr {
+int borrow_sheet(fr_ctx* ctx, int nsubs, int* device, SheetArgs* sh, NbrMap* nm) {
+    if (ctx->S < 0) return fail(ctx, FR_ERR_INVALID, "fr_dmx_set_sheet: no sheet");
+    CK(hipSetDevice(ctx->device));
+    *sh = SheetArgs{ctx->S, ctx->n_names, ctx->L1u, ctx->L2u, ctx->d_i1, ctx->d_i2, ctx->d_i2rc, ctx->d_name};
+    if (int rc = ensure_nbr(ctx, *sh, nsubs, 0)) return rc;
+    CK(hipStreamSynchronize(ctx->stream));  // the sheet upload and the map build: the demux reads them on its own stream
+    *nm = ctx->nbr;
+    *device = ctx->device;
+    return FR_OK;
+}
+}  // namespace fr

@@ -7,7 +7,9 @@
 //   dmx_count  newline count per 16-KiB tile (HBM-bound streaming read)
 //   scan       exclusive prefix of the tile counts (rocprim)
 //   dmx_index  record starts (every 4th line start) and, for R2, the code -> destination lookup
-//              in an open-addressing table of the results' fast codes
+//              in an open-addressing table of the results' fast codes; in sheet mode (fr_dmx_set_sheet)
+//              the code's fast key instead, which dmx_class_kernel (fr_kernels.hip) classifies against
+//              the sample sheet and turns into the destination: no results, no scan pass
 //   route      stable partition of the record pairs by destination (rocprim radix sort on the
 //              destination, record index as payload), output offsets (rocprim scans) and a
 //              gather-copy of both mates' record bytes into destination-major buffers
@@ -34,6 +36,7 @@ constexpr int DWG = 256;         // lanes per workgroup: 64 B each
 constexpr int DSEG = DT / DWG;
 constexpr int DHALO = 1024;      // bytes staged past the tile for headers that cross it
 constexpr int DMAXSYM = MAXSYM;  // fast key: <= 21 symbols
+constexpr u64 DMX_BATCH = 64;    // fr_dmx_records / fr_dmx_patch: from this many records on, whole-array copies
 
 __device__ __forceinline__ u32 nl_mask4(u32 w) {  // exact '\n' bytes -> bits 0..3
     const u32 t = w ^ 0x0A0A0A0Au;
@@ -141,8 +144,21 @@ __device__ __forceinline__ bool encode_fast(const u8* lds, u32 s, u32 n, u64& ke
     return bad == 0;
 }
 
+// a fast key's destination: the table's answer, or in key mode (fr_dmx_set_sheet) the key itself for
+// dmx_class_kernel, which replaces DMX_PENDING
+template <bool KEY>
+__device__ __forceinline__ int32_t key_dest(const DmxTable& tab, u64 key, u64& key_out) {
+    if constexpr (KEY) {
+        key_out = key;
+        return DMX_PENDING;
+    } else {
+        return table_get(tab, key);
+    }
+}
+
 // slow path: the header line runs past the staged bytes -> byte loop over global memory
-__device__ __noinline__ int32_t header_dest_global(const u8* buf, u64 len, u64 p, const DmxTable& tab) {
+template <bool KEY>
+__device__ __noinline__ int32_t header_dest_global(const u8* buf, u64 len, u64 p, const DmxTable& tab, u64& key_out) {
     u64 e = p, lastc = ~0ull;
     while (e < len && buf[e] != '\n') {
         if (buf[e] == ':') lastc = e;
@@ -157,14 +173,15 @@ __device__ __noinline__ int32_t header_dest_global(const u8* buf, u64 len, u64 p
         if (!sy) return FR_DMX_EXOTIC;
         key |= (u64)sy << (3 * i);
     }
-    return table_get(tab, key);
+    return key_dest<KEY>(tab, key, key_out);
 }
 
 // the code of the header line starting at tile position q: the text after the line's last ':'
 // up to its '\n' (frender.py:778) -> destination.  Word-at-a-time over the staged tile (LDS,
 // zero-padded past lds_n); '\n' and ':' found with exact SWAR byte masks.
+template <bool KEY>
 __device__ __forceinline__ int32_t header_dest(const u8* buf, u64 len, u64 tile0, u32 q, const u8* lds, u32 lds_n,
-                                               const DmxTable& tab) {
+                                               const DmxTable& tab, u64& key_out) {
     int lastc = -1, e = -1;
     u32 w = q & ~3u;
     u32 keep = (0xFu << (q & 3u)) & 0xFu;
@@ -187,7 +204,7 @@ __device__ __forceinline__ int32_t header_dest(const u8* buf, u64 len, u64 tile0
         if (col) lastc = (int)(w + 31u - __builtin_clz(col));
     }
     if (e < 0) {
-        if (tile0 + lds_n < len) return header_dest_global(buf, len, tile0 + q, tab);
+        if (tile0 + lds_n < len) return header_dest_global<KEY>(buf, len, tile0 + q, tab, key_out);
         e = (int)lds_n;  // the line ends with the data
     }
     const u32 s = lastc >= 0 ? (u32)lastc + 1u : q;
@@ -195,11 +212,13 @@ __device__ __forceinline__ int32_t header_dest(const u8* buf, u64 len, u64 tile0
     if (n == 0 || n > (u32)DMAXSYM) return FR_DMX_EXOTIC;
     u64 key;
     if (!encode_fast(lds, s, n, key)) return FR_DMX_EXOTIC;
-    return table_get(tab, key);
+    return key_dest<KEY>(tab, key, key_out);
 }
 
+// KEY (fr_dmx_set_sheet's mode): no table; a record's fast key goes to rec_key and DMX_PENDING to rec_dest
+template <bool KEY>
 __global__ __launch_bounds__(DWG) void dmx_index(const u8* buf, u64 len, u32 ntiles, const u64* tile_base,
-                                                 u64* rec_start, int32_t* rec_dest, DmxTable tab) {
+                                                 u64* rec_start, int32_t* rec_dest, DmxTable tab, u64* rec_key) {
     __shared__ __attribute__((aligned(16))) u8 lds[DT + DHALO + 32];  // +32: zero pad for word reads
     __shared__ u32 ws[DWG / 64];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -240,12 +259,20 @@ __global__ __launch_bounds__(DWG) void dmx_index(const u8* buf, u64 len, u32 nti
             const u64 p = tile0 + (u64)tid * DSEG + j + 1;
             if ((L & 3ull) == 0 && p < len) {
                 rec_start[L >> 2] = p;
-                if (rec_dest) rec_dest[L >> 2] = header_dest(buf, len, tile0, (u32)(p - tile0), lds, lds_n, tab);
+                if (rec_dest) {
+                    u64 key = 0;
+                    rec_dest[L >> 2] = header_dest<KEY>(buf, len, tile0, (u32)(p - tile0), lds, lds_n, tab, key);
+                    if constexpr (KEY) rec_key[L >> 2] = key;
+                }
             }
         }
         if (t == 0 && tid == 0 && len > 0) {  // the first line of the file
             rec_start[0] = 0;
-            if (rec_dest) rec_dest[0] = header_dest(buf, len, tile0, 0u, lds, lds_n, tab);
+            if (rec_dest) {
+                u64 key = 0;
+                rec_dest[0] = header_dest<KEY>(buf, len, tile0, 0u, lds, lds_n, tab, key);
+                if constexpr (KEY) rec_key[0] = key;
+            }
         }
         __syncthreads();
     }
@@ -336,6 +363,15 @@ struct fr_dmx {
     u64* tkeys = nullptr;
     int32_t* tvals = nullptr;
     u64 tmask = 0;
+    // sheet mode (fr_dmx_set_sheet): the borrowed sheet and maps, the destinations, every R2 record's fast key
+    bool key_mode = false;
+    SheetArgs sheet{};
+    NbrMap nbr{};
+    int nsubs = 0;
+    int32_t* row_dest = nullptr;
+    DmxClassDest class_dest{};
+    u64* rkey = nullptr;
+    u64 rkey_cap = 0;
     // per mate: data, record starts (+ sentinel), destinations (R2)
     u8* data[2] = {nullptr, nullptr};
     u64 cap[2] = {0, 0};
@@ -402,7 +438,7 @@ void fr_dmx_destroy(fr_dmx* d) {
     if (d->stream) (void)hipStreamSynchronize(d->stream);
     void* p[] = {d->tkeys, d->tvals, d->data[0], d->data[1], d->rs[0], d->rs[1], d->dest, d->out[0], d->out[1],
                  d->k_in, d->k_out, d->i_in, d->perm, d->first_pos, d->l1, d->l2, d->o1, d->o2, d->off1, d->off2,
-                 d->tmp, d->cnt, d->base, d->fe};
+                 d->tmp, d->cnt, d->base, d->fe, d->row_dest, d->rkey};
     for (void* x : p)
         if (x) (void)hipFree(x);
     for (fr_defl* z : d->defl) fr_defl_destroy(z);
@@ -414,6 +450,7 @@ const char* fr_dmx_last_error(const fr_dmx* d) { return d ? d->err.c_str() : "nu
 
 int fr_dmx_set_table(fr_dmx* d, const uint64_t* keys, const int32_t* vals, uint64_t n) {
     DK(hipSetDevice(d->device));
+    d->key_mode = false;
     if (d->tkeys) DK(hipFree(d->tkeys));
     if (d->tvals) DK(hipFree(d->tvals));
     d->tkeys = nullptr;
@@ -438,6 +475,33 @@ int fr_dmx_set_table(fr_dmx* d, const uint64_t* keys, const int32_t* vals, uint6
         DK(hipFree(k));
         DK(hipFree(v));
     }
+    return FR_OK;
+}
+
+int fr_dmx_set_sheet(fr_dmx* d, fr_ctx* ctx, int num_subs, const int32_t* row_dest, int n_rows,
+                     const int32_t class_dest[4]) {
+    if (!ctx || !class_dest || n_rows < 0 || (n_rows && !row_dest))
+        return d->err = "fr_dmx_set_sheet: null context or destinations", FR_ERR_INVALID;
+    d->key_mode = false;
+    int device = -1;
+    SheetArgs sh{};
+    NbrMap nm{};
+    if (int rc = borrow_sheet(ctx, num_subs, &device, &sh, &nm))
+        return d->err = std::string("fr_dmx_set_sheet: ") + fr_last_error(ctx), rc;
+    if (device != d->device) return d->err = "fr_dmx_set_sheet: the context is on another device", FR_ERR_INVALID;
+    if (n_rows != std::max(sh.S, 0))
+        return d->err = "fr_dmx_set_sheet: n_rows differs from the sheet's rows", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    DK(hipStreamSynchronize(d->stream));  // an earlier window may still read the old destinations
+    if (d->row_dest) DK(hipFree(d->row_dest));
+    d->row_dest = nullptr;
+    DK(hipMalloc((void**)&d->row_dest, std::max(n_rows, 1) * sizeof(int32_t)));
+    if (n_rows) DK(hipMemcpy(d->row_dest, row_dest, n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    for (int k = 0; k < 4; ++k) d->class_dest.v[k] = class_dest[k];
+    d->sheet = sh;
+    d->nbr = nm;
+    d->nsubs = num_subs;
+    d->key_mode = true;
     return FR_OK;
 }
 
@@ -471,10 +535,17 @@ static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_re
     d->nrec[mate] = nrec;
     *n_records = nrec;
     DK(hipMemcpyAsync(d->rs[mate] + nrec, &d->len[mate], 8, hipMemcpyHostToDevice, d->stream));  // sentinel
-    if (ntiles) {
+    if (ntiles && mate == 1 && d->key_mode) {
+        DK(ensure(&d->rkey, d->rkey_cap, nrec + 1));
+        hipLaunchKernelGGL(dmx_index<true>, dim3(std::min<u32>(ntiles, 4096)), dim3(DWG), 0, d->stream, buf, len,
+                           ntiles, d->base, d->rs[mate], d->dest, DmxTable{nullptr, nullptr, 0}, d->rkey);
+        DK(hipGetLastError());
+        DK(launch_dmx_classify(d->rkey, d->dest, nrec, d->sheet, d->nsubs, d->nbr, d->row_dest, d->class_dest,
+                               d->stream));
+    } else if (ntiles) {
         DmxTable tab{d->tkeys, d->tvals, d->tmask};
-        hipLaunchKernelGGL(dmx_index, dim3(std::min<u32>(ntiles, 4096)), dim3(DWG), 0, d->stream, buf, len, ntiles,
-                           d->base, d->rs[mate], mate == 1 ? d->dest : nullptr, tab);
+        hipLaunchKernelGGL(dmx_index<false>, dim3(std::min<u32>(ntiles, 4096)), dim3(DWG), 0, d->stream, buf, len,
+                           ntiles, d->base, d->rs[mate], mate == 1 ? d->dest : nullptr, tab, (u64*)nullptr);
         DK(hipGetLastError());
     }
     DK(hipStreamSynchronize(d->stream));
@@ -514,8 +585,18 @@ int fr_dmx_load_device(fr_dmx* d, int mate, const uint8_t* dev_data, uint64_t le
 int fr_dmx_records(fr_dmx* d, int mate, const uint64_t* recs, uint64_t n, uint64_t* starts, uint64_t* ends) {
     DK(hipSetDevice(d->device));
     std::vector<u64> all;
-    for (u64 k = 0; k < n; ++k) {
+    for (u64 k = 0; k < n; ++k)
         if (recs[k] >= d->nrec[mate]) return d->err = "record index out of range", FR_ERR_INVALID;
+    if (n >= DMX_BATCH) {  // many records (a file of lower-case codes: every one exotic): the whole array in one copy
+        all.resize(d->nrec[mate] + 1);
+        DK(hipMemcpy(all.data(), d->rs[mate], all.size() * 8, hipMemcpyDeviceToHost));
+        for (u64 k = 0; k < n; ++k) {
+            starts[k] = all[recs[k]];
+            ends[k] = all[recs[k] + 1];
+        }
+        return FR_OK;
+    }
+    for (u64 k = 0; k < n; ++k) {
         u64 se[2];
         DK(hipMemcpy(se, d->rs[mate] + recs[k], 16, hipMemcpyDeviceToHost));
         starts[k] = se[0];
@@ -541,10 +622,17 @@ int fr_dmx_exotic(fr_dmx* d, uint64_t n_pairs, uint64_t* recs, uint64_t cap, uin
 
 int fr_dmx_patch(fr_dmx* d, const uint64_t* recs, const int32_t* dest, uint64_t n) {
     DK(hipSetDevice(d->device));
-    for (u64 k = 0; k < n; ++k) {
+    for (u64 k = 0; k < n; ++k)
         if (recs[k] >= d->nrec[1]) return d->err = "record index out of range", FR_ERR_INVALID;
-        DK(hipMemcpyAsync(d->dest + recs[k], dest + k, 4, hipMemcpyHostToDevice, d->stream));
+    if (n >= DMX_BATCH) {  // many records: the whole array there and back, two copies
+        std::vector<int32_t> all(d->nrec[1]);
+        DK(hipMemcpy(all.data(), d->dest, all.size() * 4, hipMemcpyDeviceToHost));
+        for (u64 k = 0; k < n; ++k) all[recs[k]] = dest[k];
+        DK(hipMemcpy(d->dest, all.data(), all.size() * 4, hipMemcpyHostToDevice));
+        return FR_OK;
     }
+    for (u64 k = 0; k < n; ++k)
+        DK(hipMemcpyAsync(d->dest + recs[k], dest + k, 4, hipMemcpyHostToDevice, d->stream));
     DK(hipStreamSynchronize(d->stream));
     return FR_OK;
 }

@@ -6,6 +6,8 @@
 
 #include <vector>
 
+struct fr_ctx;
+
 namespace fr {
 
 typedef uint8_t u8;
@@ -359,6 +361,16 @@ u64 nbr_codes_per_row(int L, int nsubs);
 // (re)build the maps of nm (already allocated and zeroed) for the sheet sh; canon = 3 x S value ids
 hipError_t launch_nbr_build(const SheetArgs& sh, const int32_t* canon, int nsubs, int rc, const NbrMap& nm,
                             hipStream_t s);
+// demux key mode (fr_demux.hip, fr_dmx_set_sheet): rec_dest[u] == DMX_PENDING marks a record whose fast key
+// dmx_index left in rec_key[u]; the launch replaces it with the record's destination: FR_DMX_NOPLUS /
+// FR_DMX_LEN1 / FR_DMX_LEN2 where classify_kernel reports error 3 / 1 / 2, row_dest[row] for a demuxable
+// code, class_dest[cls] otherwise.  Every other rec_dest entry is left as it is.
+constexpr int32_t DMX_PENDING = INT32_MIN;
+struct DmxClassDest {
+    int32_t v[4];        // by CLS_*
+};
+hipError_t launch_dmx_classify(const u64* rec_key, int32_t* rec_dest, u64 n, SheetArgs sh, int nsubs,
+                               const NbrMap& nm, const int32_t* row_dest, DmxClassDest cd, hipStream_t s);
 hipError_t launch_classify_cp(int n, const u32* q1, const int32_t* q1len, const u32* q2, const int32_t* q2len,
                               int stride, int S, const u32* s1, const int32_t* s1len, const u32* s2,
                               const int32_t* s2len, const u32* s2rc, const int32_t* name, int nsubs, int rc,
@@ -394,5 +406,8 @@ constexpr u64 BGZF_MAX_IN = 1ull << 30;  // compressed bytes of a BGZF file for 
 bool bgzf_member_table(const u8* data, size_t n, std::vector<BgzfMember>& out);
 // fr_deflate.hip: the operator "feed n zero bytes into the raw CRC-32 register", byte-sliced (4 x 256 words)
 void crc_shift_table(u64 n, u32* T);
+// fr_api.hip, for fr_dmx_set_sheet: the device sheet of ctx and its neighbourhood maps for nsubs (built by the
+// lazy builder when they are not current), complete on the device when the call returns
+int borrow_sheet(::fr_ctx* ctx, int nsubs, int* device, SheetArgs* sh, NbrMap* nm);
 
 }  // namespace fr

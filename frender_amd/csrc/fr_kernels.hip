@@ -20,6 +20,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "../../include/frender_amd.h"
 #include "fr_internal.h"
 
 namespace fr {
@@ -3355,6 +3356,90 @@ hipError_t launch_classify(const u64* keys, const u64* counts, u64 n, SheetArgs 
     else
         hipLaunchKernelGGL(classify_kernel<u64>, dim3((u32)grid), dim3(CLS_WG), lds, s, keys, counts, n, sh, nsubs, rc,
                            o, nm, sheet_in_lds, names_in_lds, zero_next, zero_n, err_flag);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// demux key mode (fr_dmx_set_sheet): one lane per R2 record of a window, classified from its fast key as
+// classify_kernel classifies a unique code without rc, and turned into the record's destination at once.
+// No LDS: a code takes the three map probes; the exact row scan behind them (maps off, or a code near
+// several distinct sheet values) reads the rows by scalar loads with a uniform row index
+// (class_pair_s), so a sheet of any size takes the same path and registers alone bound the occupancy.
+// ------------------------------------------------------------------------------------
+// classify_kernel's per-key steps as helpers.  (classify_kernel keeps its own inline text: calling these from
+// it cost one more VGPR per lane in both instantiations, 51 -> 52 and 57 -> 58.)
+// A fast key (symbols A1 C2 G3 T4 N5 '+'6, folded they equal the sheet's a1..n5) split at '+' like
+// idx1, idx2 = code.split("+")[0:2] (frender.py:306): false without a '+'.
+__device__ __forceinline__ bool split_fast_key(u64 key, int& n1, int& n2, u64& q1, u64& q2) {
+    // SWAR over the 21 3-bit groups: len = symbols before the first empty group; the '+'
+    // groups (== 6) among them give p1, p2 (no per-symbol loop)
+    constexpr u64 G0 = 0x1249249249249249ull & ((1ull << 63) - 1ull);  // bit 0 of each group
+    const u64 nz = (key | (key >> 1) | (key >> 2)) & G0;                // groups holding a symbol
+    const u64 empty = ~nz & G0;
+    const int len = empty ? (int)(__builtin_ctzll(empty) / 3) : MAXSYM;
+    const u64 x = key ^ (G0 * 6ull);                                    // '+' groups become 0
+    u64 pm = ~(x | (x >> 1) | (x >> 2)) & G0;
+    pm &= len < MAXSYM ? (1ull << (3 * len)) - 1ull : ~0ull;
+    const int p1 = pm ? (int)(__builtin_ctzll(pm) / 3) : -1;
+    pm &= pm - 1ull;
+    const int p2 = pm ? (int)(__builtin_ctzll(pm) / 3) : MAXSYM;
+    const bool plus = p1 >= 0;
+    if (plus) {
+        n1 = p1;
+        const int e2 = p2 < len ? p2 : len;
+        n2 = e2 - p1 - 1;
+        q1 = n1 ? (key & ((1ull << (3 * n1)) - 1ull)) : 0ull;
+        q2 = n2 ? ((key >> (3 * (p1 + 1))) & ((1ull << (3 * n2)) - 1ull)) : 0ull;
+    }
+    return plus;
+}
+
+// the length asserts (frender.py:227-229), idx1 list first: 1 idx1, 2 idx2, 0 none
+__device__ __forceinline__ int length_error(const SheetArgs& sh, int n1, int n2) {
+    if (sh.S > 0 && (sh.L1u == -2 || sh.L1u != n1)) return 1;
+    if (sh.S > 0 && (sh.L2u == -2 || sh.L2u != n2)) return 2;
+    return 0;
+}
+
+template <typename W>
+__global__ __launch_bounds__(CLS_WG) void dmx_class_kernel(const u64* __restrict__ rec_key, int32_t* rec_dest, u64 n,
+                                                           SheetArgs sh, int nsubs, NbrMap nm,
+                                                           const int32_t* __restrict__ row_dest, DmxClassDest cd) {
+    for (u64 u = blockIdx.x * (u64)CLS_WG + threadIdx.x; u < n; u += (u64)gridDim.x * CLS_WG) {
+        if (rec_dest[u] != DMX_PENDING) continue;  // exotic: the host resolves it
+        int n1 = 0, n2 = 0;
+        u64 q1 = 0, q2 = 0;
+        int32_t d;
+        if (!split_fast_key(rec_key[u], n1, n2, q1, q2)) {
+            d = FR_DMX_NOPLUS;
+        } else if (const int err = length_error(sh, n1, n2)) {
+            d = err == 1 ? FR_DMX_LEN1 : FR_DMX_LEN2;
+        } else {
+            int m1, m2, cls, row, rm2, rcls, rrow;
+            int a1 = -2, a2 = -2, a3 = -1;
+            if (nm.on) nbr_find3(nm, q1, q2, false, a1, a2, a3);
+            if (a1 != -2 && a2 != -2) class_pair_nbr(nm, a1, a2, a3, m1, m2, cls, row, rm2, rcls, rrow);
+            else class_pair_s<W, false>((W)q1, (W)q2, sh.i1, sh.i2, sh.i2rc, sh.S, nsubs, m1, m2, cls, row, rm2, rcls,
+                                        rrow);
+            d = cls == CLS_DEMUX ? row_dest[row] : cls == CLS_HOP ? cd.v[CLS_HOP] : cls == CLS_AMBIG ? cd.v[CLS_AMBIG]
+                                                                                                     : cd.v[CLS_UNDET];
+        }
+        rec_dest[u] = d;
+    }
+}
+
+hipError_t launch_dmx_classify(const u64* rec_key, int32_t* rec_dest, u64 n, SheetArgs sh, int nsubs,
+                               const NbrMap& nm, const int32_t* row_dest, DmxClassDest cd, hipStream_t s) {
+    if (!n) return hipSuccess;
+    // u32 distances when every sheet entry (and so every query that passes the length checks) has <= 10 symbols
+    const bool narrow = sh.S > 0 && sh.L1u >= 0 && sh.L1u <= 10 && sh.L2u >= 0 && sh.L2u <= 10;
+    const u64 grid = std::max<u64>(1, std::min<u64>((n + CLS_WG - 1) / CLS_WG, 2048));
+    if (narrow)
+        hipLaunchKernelGGL(dmx_class_kernel<u32>, dim3((u32)grid), dim3(CLS_WG), 0, s, rec_key, rec_dest, n, sh, nsubs,
+                           nm, row_dest, cd);
+    else
+        hipLaunchKernelGGL(dmx_class_kernel<u64>, dim3((u32)grid), dim3(CLS_WG), 0, s, rec_key, rec_dest, n, sh, nsubs,
+                           nm, row_dest, cd);
     return hipGetLastError();
 }
 

@@ -6,6 +6,10 @@ lines and failure modes.  Per file pair, the decoded R1 and R2 text goes to the 
 R2 code of each pair against the results and gathers both mates' records destination-major;
 the host inflates, resolves the rare codes outside the fast alphabet, raises the reference's
 errors and gzips each destination's bytes into its writer pair (threads: zlib releases the GIL).
+
+`demux -b SHEET -n N` (not in the reference) needs no results: the GPU classifies every pair's code
+against the sample sheet as `scan -n N` classifies it (fr_dmx_set_sheet, SheetMode below) and the rest is
+the same, so one pass over the inputs writes what scan + demux -r write in two.
 """
 from __future__ import annotations
 
@@ -24,7 +28,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import gz_format, parse_files
+from .host import demux_mode, get_indexes, gz_format, parse_files
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
 # the column order `scan` itself writes (frender.py:482-501, report_analysis)
@@ -332,11 +336,124 @@ def _tail(parts, start: int) -> list:
 STAGE_TIMES = {}  # seconds per stage of _demux_pair's windows (demux --stage-times prints them)
 
 
-def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of, writers, window):
+def plan_destinations(ids, samples: bool, undeter: bool, index_hop: bool, ambiguous: bool):
+    """frender.py:755-810's writers as destination ids: (names, route_of).  names[k] is destination k's
+    file name stem -- the sample ids in the given order, then the class destinations -- and
+    route_of((read_type, sample_id)) is a pair's destination, FR_DMX_MISSING ("Couldn't find barcode") or
+    FR_DMX_BADTYPE ("Unrecognized read type")."""
+    undeter_name = f"Undetermined{'-ambiguous' if ambiguous else ''}{'-index-hop' if index_hop else ''}"
+    names = []
+
+    def new(name):
+        names.append(name)
+        return len(names) - 1
+
+    sample_dest = {sid: new(sid) for sid in ids} if samples else None
+    undeter_dest = new(undeter_name) if undeter else None
+    hop_dest = new("Index-hop") if index_hop else undeter_dest
+    amb_dest = new("Ambiguous") if ambiguous else undeter_dest
+
+    def route_of(row) -> int:  # frender.py:779-810
+        rtype, sid = row
+        if rtype == "demuxable" and sample_dest:
+            return sample_dest.get(sid, _lib.FR_DMX_MISSING)  # KeyError -> "Couldn't find barcode"
+        if rtype == "index_hop" and hop_dest is not None:
+            return hop_dest
+        if rtype == "ambiguous" and amb_dest is not None:
+            return amb_dest
+        if rtype == "undetermined" and undeter_dest is not None:
+            return undeter_dest
+        return _lib.FR_DMX_BADTYPE
+
+    return names, route_of
+
+
+def sheet_destinations(sheet_ids, route_of) -> tuple:
+    """fr_dmx_set_sheet's tables for `demux -b`: (row_dest, class_dest).  row_dest[row] takes a code that
+    is demuxable to sheet row `row`, class_dest[class] (_lib.CLASS_NAMES' order) every other code; both
+    come from route_of, so the flags' fallbacks and exits are the -r mode's."""
+    row_dest = np.array([route_of(("demuxable", sid)) for sid in sheet_ids], dtype=np.int32)
+    class_dest = np.array([_lib.FR_DMX_BADTYPE if name == "demuxable" else route_of((name, ""))
+                           for name in _lib.CLASS_NAMES], dtype=np.int32)
+    return row_dest, class_dest
+
+
+class SheetMode:
+    """`demux -b SHEET -n N`: every pair's code is classified against the sample sheet as `scan -n N`
+    classifies it (frender.py:214-291), per record on the GPU (fr_dmx_set_sheet); no results file.  This
+    object is the host's part: the sheet context of this process's GPU, the codes outside the fast
+    alphabet (case-folded, classified over code points as scan.process classifies exotic codes, each
+    distinct string once for the whole run) and the exceptions scan raises."""
+    _ERR = {_lib.FR_DMX_LEN1: 1, _lib.FR_DMX_LEN2: 2, _lib.FR_DMX_NOPLUS: 3}
+
+    def __init__(self, indexes: dict, num_subs: int, route_of):
+        self.idx1, self.idx2, self.ids = list(indexes["idx1"]), list(indexes["idx2"]), list(indexes["id"])
+        self.num_subs = int(num_subs)
+        self.route_of = route_of
+        self.memo = {}       # exotic code -> destination or FR_DMX_LEN1 / _LEN2 / _NOPLUS
+        self.classified = 0  # exotic strings sent to the classifier (each distinct one once)
+        self.ctx = None
+        self.own_ctx = False
+
+    def bind(self, dmx, device: int, ctx=None):
+        """Upload the sheet to a context of `device` (a small one of our own unless the caller has one: it
+        never tallies) and put dmx into sheet mode."""
+        from .host import reverse_complement
+        from .scan import _sheet_names
+        if ctx is None:
+            ctx = _lib.Context(device, chunk_bytes=1 << 20, table_slots=1 << 10)
+            self.own_ctx = True
+        self.ctx = ctx
+        names, name_id = _sheet_names(self.ids)
+        ctx.set_sheet(self.idx1, self.idx2, [reverse_complement(x) for x in self.idx2], name_id, len(names))
+        row_dest, class_dest = sheet_destinations(self.ids, self.route_of)
+        dmx.set_sheet(ctx, self.num_subs, row_dest, class_dest)
+
+    def close(self):
+        if self.own_ctx and self.ctx is not None:
+            self.ctx.close()
+        self.ctx = None
+
+    def resolve(self, codes) -> list:
+        """Destinations of exotic codes (scan.process's exotic branch: split at '+', case-fold,
+        classify_cp, the same error rules)."""
+        new = [c for c in dict.fromkeys(codes) if c not in self.memo]
+        q1, q2, todo = [], [], []
+        for c in new:
+            parts = c.split("+")
+            if len(parts) < 2:
+                self.memo[c] = _lib.FR_DMX_NOPLUS
+                continue
+            todo.append(c)
+            q1.append(parts[0].lower())
+            q2.append(parts[1].lower())
+        if todo:
+            self.classified += len(todo)
+            out = self.ctx.classify_cp(q1, q2, self.num_subs, False)
+            for k, c in enumerate(todo):
+                err = int(out["err"][k])
+                if err:
+                    self.memo[c] = {1: _lib.FR_DMX_LEN1, 2: _lib.FR_DMX_LEN2}.get(err, _lib.FR_DMX_NOPLUS)
+                    continue
+                name = _lib.CLASS_NAMES[int(out["cls"][k])]
+                sid = self.ids[int(out["row"][k])] if name == "demuxable" else ""
+                self.memo[c] = self.route_of((name, sid))
+        return [self.memo[c] for c in codes]
+
+    def error(self, code: str, val: int):
+        """The exception scan raises for a code with classification error val (None: not such a value)."""
+        from .scan import _classification_error
+        which = self._ERR.get(val)
+        return None if which is None else _classification_error(code, which, self.idx1, self.idx2)
+
+
+def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of, writers, window, sheet=None,
+                hit=None):
     """One R1/R2 pair in record-aligned windows: the GPU indexes both windows, the complete
     record pairs are routed, and the bytes after the last routed record carry into the next
     window.  Pairing stops when either mate runs out of records (zip, frender.py:777).  The mates
-    inflate on the native pool gz (files i1, i2)."""
+    inflate on the native pool gz (files i1, i2).  sheet (SheetMode): `demux -b`, no results; hit: a set
+    that collects the destinations pairs were routed to."""
     streams = [text_chunks(read1_file, gz, i1), text_chunks(read2_file, gz, i2)]
     bufs = [[], []]  # each mate's window as a list of decoded blocks (never joined on the host)
     eof = [False, False]
@@ -371,10 +488,13 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
             if ex.size:  # codes outside the fast alphabet: resolve by string
                 starts, _ = dmx.records(1, ex)
                 dest = []
-                for s in starts.tolist():
-                    code = _line_at(bufs[1], s).split(b":")[-1].decode("utf-8")
-                    row = results.get(code)
-                    dest.append(_lib.FR_DMX_MISSING if row is None else route_of(row))
+                if sheet is not None:
+                    dest = sheet.resolve([_line_at(bufs[1], s).split(b":")[-1].decode("utf-8") for s in starts.tolist()])
+                else:
+                    for s in starts.tolist():
+                        code = _line_at(bufs[1], s).split(b":")[-1].decode("utf-8")
+                        row = results.get(code)
+                        dest.append(_lib.FR_DMX_MISSING if row is None else route_of(row))
                 dmx.patch(ex, np.array(dest, dtype=np.int32))
             first, val, b1, b2 = dmx.route(len(writers), n_pairs)
             t3 = clock()
@@ -383,7 +503,12 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 code = _line_at(bufs[1], int(s[0])).split(b":")[-1].decode("utf-8")
                 if val == _lib.FR_DMX_MISSING:
                     raise SystemExit(f"Couldn't find barcode {code} in supplied frender result file!")
+                err = sheet.error(code, val) if sheet is not None else None
+                if err is not None:
+                    raise err
                 raise SystemExit("Unrecognized read type found in supplied frender result file!")
+            if hit is not None:
+                hit.update(np.nonzero(b1 + b2)[0].tolist())
             if isinstance(writers[0]["R1"], _BgzfDevice):  # the GPU makes every destination's BGZF members
                 z1, o1 = dmx.deflate_bgzf(0, len(writers))
                 z2, o2 = dmx.deflate_bgzf(1, len(writers))
@@ -447,9 +572,27 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
             st.close()
 
 
-def frender_demux(args, dev=None) -> None:
-    """frender.py:733-814 with the per-record loop on the GPU."""
+def _drop_unhit(names, lazy, hit, out_dir, infix) -> None:
+    """`demux -b`: a sample's file pair exists iff a pair was routed to it, as in -r mode, where the sample
+    ids come from the results.  The writers were opened for every sheet id: remove the pairs of the ids in
+    `lazy` that `hit` lacks (after their writers are closed)."""
+    for k in sorted(lazy - hit):
+        for read in ("R1", "R2"):
+            try:
+                os.unlink(out_path(names[k], out_dir, infix, read))
+            except FileNotFoundError:
+                pass
+
+
+NO_SAMPLES_WARNING = "Warning: no demuxable sample ids found in the supplied frender result file!"
+
+
+def frender_demux(args, dev=None, ctx=None) -> None:
+    """frender.py:733-814 with the per-record loop on the GPU.  args.r: the classes come from a scan's result
+    file, as in the reference; args.b with args.n (and args.r None): from the sample sheet, one pass (SheetMode).
+    dev: a caller's _lib.Demux; ctx: a caller's sheet context for args.b (tests: one with tuning)."""
     t_start = time.perf_counter()
+    mode = demux_mode(args)
     fmt = gz_format(args)
     index_hop = not args.no_index_hop
     ambiguous = not args.no_ambiguous
@@ -461,50 +604,40 @@ def frender_demux(args, dev=None) -> None:
         print(f"Warning: --gz-level {args.gz_level} has no effect with --gz-writer gpu (the GPU writer's streams "
               "are no larger than level 9's); use --gz-writer libdeflate or zlib for another level", file=sys.stderr)
     infix = args.o
-    undeter_name = f"Undetermined{'-ambiguous' if ambiguous else ''}{'-index-hop' if index_hop else ''}"
 
     from .dist import world_group
     group = None if dev is not None else world_group()  # demux --gpus N: one rank of N
     lead = group is None or group.get_rank() == 0
 
-    result_file = Path(args.r)
-    if not Path.is_file(result_file):
-        raise SystemExit(f"File {result_file} not found")
-    results = parse_results_file(result_file, strict=getattr(args, "strict_header", False))
-    ids = sorted({sid for _, sid in results.values()} - {""})
-    if (not ids) & samples and lead:
-        print("Warning: no demuxable sample ids found in the supplied frender result file!")
+    results = indexes = None
+    if mode == "r":
+        result_file = Path(args.r)
+        if not Path.is_file(result_file):
+            raise SystemExit(f"File {result_file} not found")
+        results = parse_results_file(result_file, strict=getattr(args, "strict_header", False))
+        ids = sorted({sid for _, sid in results.values()} - {""})
+        if (not ids) & samples and lead:
+            print(NO_SAMPLES_WARNING)
+    else:  # the sheet as scan -b reads it; which ids have reads is known after the last pair only
+        indexes = get_indexes(Path(args.b))
+        ids = sorted(set(indexes["id"]) - {""})
 
     if group is None:
         os.mkdir(args.d)
     else:
         _mkdir_everywhere(group, args.d)
-    writers = []  # destination id -> writer pair (N ranks: its name; rank 0 writes the files at the end)
+    names, route_of = plan_destinations(ids, samples, undeter, index_hop, ambiguous)
+    # destination id -> writer pair (N ranks: its name; rank 0 writes the files at the end)
+    writers = [open_files(name, args.d, infix, level, kind) for name in names] if group is None else names
+    sheet = SheetMode(indexes, args.n, route_of) if mode == "b" else None
+    lazy = set(range(len(ids))) if sheet is not None and samples else set()  # sample destinations (-b: kept if hit)
+    hit = set()
 
-    def new_writers(name):
-        writers.append(open_files(name, args.d, infix, level, kind) if group is None else name)
-        return len(writers) - 1
-
-    sample_dest = {sid: new_writers(sid) for sid in ids} if samples else None
-    undeter_dest = new_writers(undeter_name) if undeter else None
-    hop_dest = new_writers("Index-hop") if index_hop else undeter_dest
-    amb_dest = new_writers("Ambiguous") if ambiguous else undeter_dest
-
-    def route_of(row) -> int:  # frender.py:779-810
-        rtype, sid = row
-        if rtype == "demuxable" and sample_dest:
-            return sample_dest.get(sid, _lib.FR_DMX_MISSING)  # KeyError -> "Couldn't find barcode"
-        if rtype == "index_hop" and hop_dest is not None:
-            return hop_dest
-        if rtype == "ambiguous" and amb_dest is not None:
-            return amb_dest
-        if rtype == "undetermined" and undeter_dest is not None:
-            return undeter_dest
-        return _lib.FR_DMX_BADTYPE
-
-    codes = list(results.keys())
-    keys, fast = _lib.pack_fast(codes)
-    vals = np.array([route_of(results[c]) for c in codes], dtype=np.int32)
+    keys = vals = fast = None
+    if mode == "r":
+        codes = list(results.keys())
+        keys, fast = _lib.pack_fast(codes)
+        vals = np.array([route_of(results[c]) for c in codes], dtype=np.int32)
 
     if len(args.files) == 1:
         file = Path(args.files[0])
@@ -520,8 +653,8 @@ def frender_demux(args, dev=None) -> None:
 
     window = int(getattr(args, "window", None) or (512 << 20))  # decoded bytes per mate per GPU pass
     if group is not None:
-        return _demux_ranks(group, args, dev, pairs, results, route_of, keys[fast], vals[fast], writers, window, level,
-                            infix, kind)
+        return _demux_ranks(group, args, dev, pairs, results, route_of, None if sheet else keys[fast],
+                            None if sheet else vals[fast], writers, window, level, infix, kind, sheet, lazy)
     # with the GPU compressing, the host's cores inflate (a big single-member file in parallel); the
     # pool's workers start at once, so the first blocks decode while the device context comes up
     paths = [str(f) for pr in pairs for f in pr]
@@ -535,11 +668,17 @@ def frender_demux(args, dev=None) -> None:
         raise
     pool = ThreadPoolExecutor(max_workers=max(2, min(32, len(writers) * 2)))
     try:
-        dmx.set_table(keys[fast], vals[fast])
+        if sheet is not None:
+            sheet.bind(dmx, _device_index(None), ctx)
+        else:
+            dmx.set_table(keys[fast], vals[fast])
         STAGE_TIMES["setup"] = time.perf_counter() - t_start  # results, writers, device table, pool
         for k, (read1_file, read2_file) in enumerate(pairs):
             print(f"Demultiplexing {read1_file.name}...")
-            _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers, window)
+            _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers, window,
+                        sheet, hit)
+        if sheet is not None and samples and not (hit & lazy):
+            print(NO_SAMPLES_WARNING)  # known only now: no pair was demuxable
     finally:
         t_end = time.perf_counter()
         gz.close()
@@ -550,9 +689,14 @@ def frender_demux(args, dev=None) -> None:
         for w in writers:
             for f in w.values():
                 f.close()
+        _drop_unhit(names, lazy, hit, args.d, infix)
         t_files = time.perf_counter()
         if dev is None:
             dmx.close()
+        elif sheet is not None:
+            dmx.set_table(np.zeros(0, np.uint64), np.zeros(0, np.int32))  # end the borrow of the sheet context
+        if sheet is not None:
+            sheet.close()
         STAGE_TIMES["finish: files"] = t_files - t_end - STAGE_TIMES["finish: inflate pool"] - STAGE_TIMES["finish: writer pool"]
         STAGE_TIMES["finish"] = time.perf_counter() - t_end  # last writes, closes
         STAGE_TIMES["total"] = time.perf_counter() - t_start
@@ -609,7 +753,8 @@ def _mkdir_everywhere(group, path):
         raise PeerFailed()
 
 
-def _demux_ranks(group, args, dev, pairs, results, route_of, keys, vals, names, window, level, infix, kind):
+def _demux_ranks(group, args, dev, pairs, results, route_of, keys, vals, names, window, level, infix, kind,
+                 sheet=None, lazy=frozenset()):
     import shutil
 
     from .dist import PeerFailed, reduce_min
@@ -625,20 +770,25 @@ def _demux_ranks(group, args, dev, pairs, results, route_of, keys, vals, names, 
         nt = _inflate_threads(kind)
         gz = _lib.GzPool(paths, threads=nt, ahead=_lib.inflate_ahead(paths, nt))
         dmx = _lib.Demux(_device_index(group))
-        dmx.set_table(keys, vals)
+        if sheet is not None:  # this rank's own sheet context: classification is stateless, nothing is exchanged
+            sheet.bind(dmx, _device_index(group))
+        else:
+            dmx.set_table(keys, vals)
         for j, k in enumerate(mine):
             d = os.path.join(parts, str(k))
             os.makedirs(d, exist_ok=True)
             writers = [open_files(n, d, infix, level, _BgzfPart if kind is _BgzfDevice else kind) for n in names]
+            hit = set()
             try:
                 _demux_pair(dmx, pool, gz, 2 * j, 2 * j + 1, pairs[k][0], pairs[k][1], results, route_of, writers,
-                            window)
+                            window, sheet, hit)
             except (Exception, SystemExit) as e:  # re-raised below if it is the first in pair order
                 failed, exc = k, e
             finally:
                 for w in writers:
                     for f in w.values():
                         f.close()
+                _drop_unhit(names, lazy, hit, d, infix)  # -b: no part for a sample this pair has no reads of
             if exc is not None:
                 break
     except (Exception, SystemExit) as e:  # before any pair (the device, the table): this rank's first pair
@@ -650,14 +800,22 @@ def _demux_ranks(group, args, dev, pairs, results, route_of, keys, vals, names, 
             gz.close()
         if dmx is not None:
             dmx.close()
+        if sheet is not None:
+            sheet.close()
     first = int(reduce_min(group, _wire(group), [failed])[0])  # every rank's pairs are done here
     last = min(first, len(pairs) - 1)
     if rank == 0:
         for k in range(last + 1):
             print(f"Demultiplexing {pairs[k][0].name}...")
-        for n in names:
+        any_sample = False
+        for i, n in enumerate(names):
             for read in ("R1", "R2"):
                 final = out_path(n, args.d, infix, read)
+                if i in lazy:  # -b: a sample's files exist iff some pair has a part for it (_drop_unhit)
+                    if not any(os.path.exists(out_path(n, os.path.join(parts, str(k)), infix, read))
+                               for k in range(last + 1)):
+                        continue
+                    any_sample = True
                 with open(final, "wb") as out:
                     for k in range(last + 1):
                         part = out_path(n, os.path.join(parts, str(k)), infix, read)
@@ -668,6 +826,8 @@ def _demux_ranks(group, args, dev, pairs, results, route_of, keys, vals, names, 
                         out.write(_lib.BGZF_EOF)
                     elif out.tell() == 0:  # no pair reached it: an empty gzip file, as the reference's writer
                         out.write(gzip.compress(b"", compresslevel=level))
+        if sheet is not None and not args.no_samples and not any_sample and first == len(pairs):
+            print(NO_SAMPLES_WARNING)  # known only now: no pair was demuxable
     reduce_min(group, _wire(group), [0])  # the parts are read: remove them
     if rank == 0:
         shutil.rmtree(parts, ignore_errors=True)

@@ -115,6 +115,23 @@ def reverse_complement(s: str) -> str:
     return s.translate(str.maketrans("ATGCNatgcn", "TACGNtacgn"))[::-1]
 
 
+def demux_mode(args) -> str:
+    """Where a demux's arguments take the classes from: "r", a scan's result file (-r), or "b", the sample
+    sheet itself (-b with -n).  Exactly one of the two; -n goes with -b only.  Called before anything is
+    opened or created (a namespace without a field means the flag was not given)."""
+    r, b, n = getattr(args, "r", None), getattr(args, "b", None), getattr(args, "n", None)
+    if r is not None and b is not None:
+        raise SystemExit("demux: -r and -b exclude each other (a scan's result file, or the sample sheet with -n)")
+    if r is None and b is None:
+        raise SystemExit("demux: one of -r (a frender scan result file) and -b (the sample sheet, with -n) is "
+                         "required")
+    if b is not None and n is None:
+        raise SystemExit("demux -b: -n (mismatches allowed, as in scan) is required")
+    if r is not None and n is not None:
+        raise SystemExit("demux -r: -n belongs to -b (the result file already holds every code's class)")
+    return "r" if r is not None else "b"
+
+
 def gz_format(args) -> str:
     """--gz-format of a demux's arguments (a namespace without it means gzip), checked against --gz-writer:
     only the GPU writer makes BGZF.  Called before anything is opened or created."""

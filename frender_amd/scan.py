@@ -302,6 +302,15 @@ def _length_error(q: str, entries) -> AssertionError:
     return AssertionError("length mismatch")  # pragma: no cover
 
 
+def _classification_error(code: str, which: int, idx1, idx2) -> Exception:
+    """The exception the reference raises for a code the classifier reported (which: 1 idx1's length,
+    2 idx2's length, 3 no '+'); `demux -b` raises the same for a record's code."""
+    if which == 3:  # idx1, idx2 = barcode.split("+")[0:2]  (frender.py:306)
+        return ValueError("not enough values to unpack (expected 2, got 1)")
+    parts = code.split("+")
+    return _length_error(parts[0], idx1) if which == 1 else _length_error(parts[1], idx2)
+
+
 def _lead(table) -> bool:
     return table.group is None or table.group.get_rank() == 0
 
@@ -363,10 +372,7 @@ def process(cores, table: UniqueTable, indexes: dict, num_subs: int, rc_mode: bo
     if errs:
         j, which = min(errs)
         code = table.codes[j] if isinstance(j, int) else j[1]
-        if which == 3:  # idx1, idx2 = barcode.split("+")[0:2]  (frender.py:306)
-            raise ValueError("not enough values to unpack (expected 2, got 1)")
-        parts = code.split("+")
-        raise _length_error(parts[0], idx1) if which == 1 else _length_error(parts[1], idx2)
+        raise _classification_error(code, which, idx1, idx2)
     if rc_mode:
         f, r = ctx.rc_counts() if fsel.size else (np.zeros(len(names), np.uint64), np.zeros(len(names), np.uint64))
         res.rc_f = f + f_add

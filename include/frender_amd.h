@@ -321,6 +321,10 @@ int fr_synth_device(fr_ctx* ctx, uint8_t* dev_out, uint64_t r0, uint64_t n, int 
 #define FR_DMX_MISSING (-1) /* code not in the results: SystemExit "Couldn't find barcode ..." (:807-810) */
 #define FR_DMX_BADTYPE (-2) /* read type with no writers: SystemExit "Unrecognized read type ..." (:803-806) */
 #define FR_DMX_EXOTIC (-3)  /* code outside the fast alphabet / > 21 chars: the host resolves it */
+/* sheet mode (fr_dmx_set_sheet) only: the code's classification error, as `scan` raises it (frender.py:227-229, :306) */
+#define FR_DMX_LEN1 (-4)    /* idx1's length differs from the sheet's: AssertionError */
+#define FR_DMX_LEN2 (-5)    /* idx2's length differs from the sheet's: AssertionError */
+#define FR_DMX_NOPLUS (-6)  /* no '+' in the code: ValueError */
 
 typedef struct fr_dmx fr_dmx;
 fr_dmx* fr_dmx_create(int device);
@@ -329,6 +333,17 @@ const char* fr_dmx_last_error(const fr_dmx* d);
 /* results table: fast-alphabet codes (3-bit packed like fr_get_unique keys) -> destination or
  * FR_DMX_BADTYPE; codes absent from the table resolve to FR_DMX_MISSING */
 int fr_dmx_set_table(fr_dmx* d, const uint64_t* keys, const int32_t* vals, uint64_t n);
+/* sheet mode, instead of a results table: every R2 record's code is classified against ctx's sheet as
+ * fr_classify classifies it with num_subs and no rc (frender.py:214-291), and the record goes to
+ * row_dest[row] (n_rows = the sheet's rows) when it is demuxable, else to class_dest[class] (0 undetermined,
+ * 1 index hop, 3 ambiguous; entry 2 is unused); these may be FR_DMX_MISSING / FR_DMX_BADTYPE.  A code with a
+ * classification error gets FR_DMX_LEN1 / _LEN2 / _NOPLUS.  ctx is a context on d's device on which
+ * fr_set_sheet has been called: d borrows its device sheet and its neighbourhood maps for num_subs (built
+ * here when they are not current; ctx's stream is synchronised once) until the next fr_dmx_set_table /
+ * fr_dmx_set_sheet / fr_dmx_destroy.  Meanwhile the caller keeps ctx alive, leaves its sheet as it is and
+ * classifies on it with no other num_subs.  fr_dmx_set_table switches back to table mode. */
+int fr_dmx_set_sheet(fr_dmx* d, fr_ctx* ctx, int num_subs, const int32_t* row_dest, int n_rows,
+                     const int32_t class_dest[4]);
 /* mate 0 = R1, 1 = R2 (R2 also resolves every record's destination); returns the record count */
 int fr_dmx_load(fr_dmx* d, int mate, const uint8_t* data, uint64_t len, uint64_t* n_records);
 /* the same over the concatenation of n_parts host buffers (a window without a host-side join) */

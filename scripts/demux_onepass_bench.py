@@ -1,0 +1,191 @@
+#!/usr/bin/env python3
+"""demux -b against scan + demux -r on BASELINE config 5's shape (96 samples, 8+8, n=1, paired R=150).
+
+Generates --files level-1 .fastq.gz file pairs of --pairs SYN-v1 read pairs in all (bench.py's --cfg5
+generator), then times whole command lines, each in a process of its own, as a user runs them:
+
+  two-pass   python -m frender_amd scan -n 1 -b sheet R1...   then   python -m frender_amd demux -r CSV files...
+  one-pass   python -m frender_amd demux -b sheet -n 1 files...
+
+The first run of each route is reported as "cold" (this process tree's first use of the GPU, the library and
+the inputs), then --runs alternating runs of both as "warm": medians and min-max.  The decoded content of every
+output file of the two routes is compared (the first runs').  Every demux runs with --stage-times; the
+per-window load+index and route stages of `demux -b`, of this tree's `demux -r` and, with --parent ROOT (a
+built checkout of the parent commit), of the parent's `demux -r` on the same inputs and results file come
+from the same alternating rounds.  Writes one JSON document (--out), stamped with the tree's source hash.
+
+Needs a GPU: there is no CPU path to time.
+"""
+import argparse
+import gzip
+import hashlib
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def run(cmd, cwd, root):
+    """(seconds, stage times or None) of one command line with `root`'s package."""
+    env = dict(os.environ, PYTHONPATH=root)
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, "-m", "frender_amd", *cmd], cwd=cwd, env=env, capture_output=True, text=True)
+    dt = time.perf_counter() - t0
+    if p.returncode:
+        raise SystemExit(f"{' '.join(cmd[:4])}... failed: {p.stderr[-2000:]}")
+    stages = next((json.loads(x) for x in reversed(p.stderr.splitlines()) if x.startswith("{")), None)
+    return dt, stages
+
+
+def digest(path) -> str:
+    h = hashlib.sha256()
+    with gzip.open(path, "rb") as f:
+        while True:
+            b = f.read(8 << 20)
+            if not b:
+                break
+            h.update(b)
+    return h.hexdigest()
+
+
+def digests(d) -> dict:
+    names = sorted(os.listdir(d))
+    with ThreadPoolExecutor(16) as ex:
+        return dict(zip(names, ex.map(digest, [os.path.join(d, n) for n in names])))
+
+
+def spread(v) -> dict:
+    return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4), "n": len(v)}
+
+
+def per_window_ms(stage_list, key) -> dict:
+    return spread([1e3 * s[key] / s["windows"] for s in stage_list])
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--pairs", type=int, default=3_200_000)
+    ap.add_argument("--files", type=int, default=16, help="file pairs")
+    ap.add_argument("--runs", type=int, default=5, help="alternating warm runs of each route (>= 5)")
+    ap.add_argument("--parent", help="root of a built checkout of the parent commit (its demux -r is timed too)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "demux_sheet_bench.json"))
+    ap.add_argument("--workdir", help="where the inputs and outputs go (default: a temporary directory)")
+    args = ap.parse_args()
+
+    import bench
+    from frender_amd import synth
+    from frender_amd._lib import source_tree_hash
+
+    own = args.workdir is None
+    d = tempfile.mkdtemp(prefix="frd_onepass_") if own else args.workdir
+    try:
+        os.makedirs(os.path.join(d, "in"), exist_ok=True)
+        sheet_csv = os.path.join(d, "sheet.csv")
+        synth.make_sheet(96, 8, 8).write_csv(sheet_csv)
+        per = args.pairs // args.files
+        jobs = [(os.path.join(d, "in", f"syn_L{p + 1:03d}_R{m}_001.fastq.gz"), p * per, per, m)
+                for p in range(args.files) for m in (1, 2)]
+        with ProcessPoolExecutor(min(16, len(os.sched_getaffinity(0)))) as ex:
+            in_bytes = sum(ex.map(bench._cfg5_write, jobs))
+        allf = sorted(os.path.join(d, "in", x) for x in os.listdir(os.path.join(d, "in")))
+        r1 = [f for f in allf if "_R1_" in f]
+        cores = str(max(1, min(16, len(os.sched_getaffinity(0)))))
+        n_pairs = per * args.files
+        serial = [0]
+
+        def two_pass(root=ROOT):
+            serial[0] += 1
+            w = os.path.join(d, f"two_{serial[0]}")
+            os.mkdir(w)
+            ts, _ = run(["scan", "-n", "1", "-c", cores, "-o", "cfg5", "-b", sheet_csv, *r1], w, root)
+            res = [os.path.join(w, x) for x in os.listdir(w) if x.endswith(".csv")][0]
+            td, st = run(["demux", "-r", res, "-d", os.path.join(w, "out"), "--stage-times", *allf], w, root)
+            return {"scan_s": ts, "demux_s": td, "total_s": ts + td, "stages": st, "dir": w, "csv": res}
+
+        def one_pass():
+            serial[0] += 1
+            w = os.path.join(d, f"one_{serial[0]}")
+            os.mkdir(w)
+            t, st = run(["demux", "-b", sheet_csv, "-n", "1", "-d", os.path.join(w, "out"), "--stage-times", *allf], w,
+                        ROOT)
+            return {"total_s": t, "stages": st, "dir": w}
+
+        def demux_r(root, csv_path):
+            serial[0] += 1
+            w = os.path.join(d, f"r_{serial[0]}")
+            os.mkdir(w)
+            t, st = run(["demux", "-r", csv_path, "-d", os.path.join(w, "out"), "--stage-times", *allf], w, root)
+            shutil.rmtree(w)
+            return {"total_s": t, "stages": st}
+
+        cold = {"two_pass": two_pass(), "one_pass": one_pass()}
+        da, db = digests(os.path.join(cold["two_pass"]["dir"], "out")), digests(os.path.join(cold["one_pass"]["dir"], "out"))
+        equal = da == db
+        csv_path = os.path.join(d, "results.csv")
+        shutil.copy(cold["two_pass"]["csv"], csv_path)
+        out_files = len(da)
+        for c in cold.values():
+            shutil.rmtree(c["dir"])
+        warm = {"two_pass": [], "one_pass": [], "parent_demux_r": []}
+        for _ in range(max(args.runs, 5)):
+            for name, fn in (("two_pass", two_pass), ("one_pass", one_pass)):
+                r = fn()
+                shutil.rmtree(r["dir"])
+                warm[name].append(r)
+            if args.parent:
+                warm["parent_demux_r"].append(demux_r(os.path.abspath(args.parent), csv_path))
+
+        def strip(r):
+            return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items() if k not in ("dir", "csv")}
+
+        two_t, one_t = [r["total_s"] for r in warm["two_pass"]], [r["total_s"] for r in warm["one_pass"]]
+        doc = {
+            "what": "demux -b -n 1 (one pass) against scan -n 1 + demux -r (two passes): whole command lines, one "
+                    "process each, on BASELINE config 5's shape",
+            "tree_hash": source_tree_hash(),
+            "workload": {"read_pairs": n_pairs, "file_pairs": args.files, "samples": 96, "index": "8+8", "n": 1,
+                         "read_len": 150, "in_gz_bytes": in_bytes, "gz_level_in": 1, "window_bytes": 512 << 20,
+                         "windows": warm["one_pass"][0]["stages"]["windows"], "host_cpus": int(cores)},
+            "outputs_equal": equal, "output_files": out_files,
+            "cold": {k: strip(v) for k, v in cold.items()},
+            "warm": {
+                "two_pass_total_s": spread(two_t),
+                "two_pass_scan_s": spread([r["scan_s"] for r in warm["two_pass"]]),
+                "two_pass_demux_s": spread([r["demux_s"] for r in warm["two_pass"]]),
+                "one_pass_total_s": spread(one_t),
+                "one_pass_over_two_pass": round(statistics.median(one_t) / statistics.median(two_t), 4),
+                "saving_over_scan_command": round((statistics.median(two_t) - statistics.median(one_t)) /
+                                                  statistics.median([r["scan_s"] for r in warm["two_pass"]]), 4),
+                "M_pairs_per_s": {"two_pass": round(n_pairs / statistics.median(two_t) / 1e6, 4),
+                                  "one_pass": round(n_pairs / statistics.median(one_t) / 1e6, 4)},
+            },
+            "stages_ms_per_window": {
+                name: {k: per_window_ms([r["stages"] for r in runs], k) for k in ("load+index", "route")}
+                for name, runs in (("demux_b", warm["one_pass"]), ("demux_r", warm["two_pass"]),
+                                   ("parent_demux_r", warm["parent_demux_r"])) if runs
+            },
+            "runs": {k: [strip(r) for r in v] for k, v in warm.items() if v},
+        }
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: doc[k] for k in ("tree_hash", "outputs_equal", "warm", "stages_ms_per_window")}))
+        if not equal:
+            raise SystemExit("the two routes' outputs differ: " +
+                             ", ".join(sorted(k for k in set(da) | set(db) if da.get(k) != db.get(k))[:10]))
+    finally:
+        if own:
+            shutil.rmtree(d, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
