@@ -8,7 +8,7 @@
 //   scan       exclusive prefix of the tile counts (rocprim)
 //   dmx_index  record starts (every 4th line start) and, for R2, the code -> destination lookup
 //              in an open-addressing table of the results' fast codes; in sheet mode (fr_dmx_set_sheet)
-//              the code's fast key instead, which dmx_class_kernel (fr_kernels.hip) classifies against
+//              the code's fast key instead, which dmx_class_kernel (fr_classify.hip) classifies against
 //              the sample sheet and turns into the destination: no results, no scan pass
 //   route      stable partition of the record pairs by destination (rocprim radix sort on the
 //              destination, record index as payload), output offsets (rocprim scans) and a

@@ -268,7 +268,7 @@ struct ClassOut {
 
 enum { CLS_UNDET = 0, CLS_HOP = 1, CLS_DEMUX = 2, CLS_AMBIG = 3 };
 
-// Classify neighbourhood maps (fr_kernels.hip, nbr_*), built per (sheet, nsubs): for each sheet list
+// Classify neighbourhood maps (fr_classify.hip, nbr_*), built per (sheet, nsubs): for each sheet list
 // (idx1, idx2, rc(idx2)) every packed code within nsubs substitutions of a distinct sheet value maps
 // to that value's id = the first row holding it; a code near several distinct values is marked
 // (vmin != vmax) and classified by the exact row scan.  The pair maps give, per (idx1 id, idx2 id),
@@ -312,7 +312,7 @@ __host__ __device__ inline u32 log_subregion(u64 key) {
     return (u32)(mix64(key) >> (64 - LOG_REGION_BITS - LOG_SUB_BITS)) & (LOG_SUBS - 1);
 }
 
-// ---- launchers (fr_kernels.hip) --------------------------------------------------
+// ---- launchers (fr_kernels.hip; the classifier's in fr_classify.hip) --------------------------------------------------
 // st != nullptr: workgroup 0 also writes the reset image of the device state (all zero, no error offset)
 hipError_t launch_table_init(GSlot* slots, u64 n, DevState* st, hipStream_t s);
 hipError_t launch_chunk_scan(const ScanArgs& a, int grid, hipStream_t s);

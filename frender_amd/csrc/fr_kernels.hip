@@ -2,9 +2,9 @@
 //
 //  tally (chunk_kernel) : frender.py:154-181 scan_file + :199-205 merge, one pass over the
 //                         decoded FASTQ bytes in HBM (R1-R4 of SURVEY.md §8.0)
-//  classify             : frender.py:214-234 (Hamming), :237-291 (classes), :294-351 (rc)
 //  table / order        : the first-occurrence-ordered merged table of :199-203
 //  synth                : SYN-v1 records (frender_amd/synth.py), device side
+// (The Hamming classifier is fr_classify.hip.)
 //
 // Design notes: the tally is HBM-bound byte work.  A workgroup takes a chunk of
 // 4-KiB wave-tiles by ticket and each of its four waves walks a quarter of it without workgroup
@@ -2896,625 +2896,6 @@ hipError_t launch_merge(Table t, DevState* st, const u64* keys, const u64* count
     if (!n) return hipSuccess;
     const int grid = (int)std::min<u64>((n + 255) / 256, 8192);
     hipLaunchKernelGGL(merge_kernel, dim3(grid), dim3(256), 0, s, t, st, keys, counts, first, n);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// classify: lane per unique code, the sheet broadcast from LDS
-// ------------------------------------------------------------------------------------
-__device__ __forceinline__ int mism(u64 q, u64 s) {  // Hamming distance of two 3-bit packed strings
-    const u64 x = q ^ s;
-    return __popcll((x | (x >> 1) | (x >> 2)) & 0x1249249249249249ull);
-}
-
-constexpr int CLS_WG = 256;
-#ifndef FR_CLS_SCALAR
-#define FR_CLS_SCALAR 1  // sheet rows by scalar loads from HBM (class_pair_s), not broadcast from LDS
-#endif
-constexpr int CLS_LDS_BYTES = 48 * 1024;  // dynamic LDS cap: sheet images + per-name rc sums
-
-__device__ __forceinline__ int mism32(u32 q, u32 s) {  // <= 10 symbols: 30 bits
-    const u32 x = q ^ s;
-    return __popc((x | (x >> 1) | (x >> 2)) & 0x09249249u);
-}
-
-template <typename W>
-__device__ __forceinline__ int mism_w(W q, W s) {
-    if constexpr (sizeof(W) == 4) return mism32(q, s);
-    else return mism(q, s);
-}
-
-// R7/R8 for one unique over every sheet row, forward idx2 and (rc) rc(idx2) in the same pass
-// (idx1's distances are shared): the first matching row of each list, |M1 ∩ M2| and its first row.
-template <typename W>
-__device__ __forceinline__ void class_pair(W q1, W q2, const W* s1, const W* s2, const W* s2rc, int S, int nsubs,
-                                           bool rc, int& m1, int& m2, int& cls, int& row, int& rm2, int& rcls,
-                                           int& rrow) {
-    m1 = -1;
-    m2 = -1;
-    rm2 = -1;
-    int both = 0, r = -1, rboth = 0, rr = -1;
-    for (int i = 0; i < S; ++i) {
-        const bool a = mism_w<W>(q1, s1[i]) <= nsubs;
-        const bool b = mism_w<W>(q2, s2[i]) <= nsubs;
-        m1 = (a && m1 < 0) ? i : m1;
-        m2 = (b && m2 < 0) ? i : m2;
-        r = (a && b && both == 0) ? i : r;
-        both += (a && b) ? 1 : 0;
-        if (rc) {
-            const bool c = mism_w<W>(q2, s2rc[i]) <= nsubs;
-            rm2 = (c && rm2 < 0) ? i : rm2;
-            rr = (a && c && rboth == 0) ? i : rr;
-            rboth += (a && c) ? 1 : 0;
-        }
-    }
-    if (m1 >= 0 && m2 >= 0) {
-        cls = both == 0 ? CLS_HOP : both == 1 ? CLS_DEMUX : CLS_AMBIG;
-        row = both == 1 ? r : -1;
-    } else {
-        cls = CLS_UNDET;
-        row = -1;
-    }
-    if (m1 >= 0 && rm2 >= 0) {
-        rcls = rboth == 0 ? CLS_HOP : rboth == 1 ? CLS_DEMUX : CLS_AMBIG;
-        rrow = rboth == 1 ? rr : -1;
-    } else {
-        rcls = CLS_UNDET;
-        rm2 = -1;
-        rrow = -1;
-    }
-    if (cls == CLS_UNDET) {  // pass A keeps matched_idx1 from the rc call (frender.py:319-323)
-        if (rcls == CLS_UNDET) m1 = -1;
-        m2 = -1;
-    }
-}
-
-// class_pair with the rows read straight from the u64 sheet arrays in HBM:
-// the row index is uniform, so every row arrives by scalar loads and the distance ops take it as a
-// scalar operand (no LDS read per row), and the bookkeeping runs only on rows some lane matches
-// (a code matches one or two rows of a well-separated sheet: the wave skips ~2/3 of the updates).
-template <typename W, bool RC>
-__device__ __forceinline__ void class_pair_s(W q1, W q2, const u64* __restrict__ s1, const u64* __restrict__ s2,
-                                             const u64* __restrict__ s2rc, int S, int nsubs, int& m1, int& m2,
-                                             int& cls, int& row, int& rm2, int& rcls, int& rrow) {
-    m1 = -1;
-    m2 = -1;
-    rm2 = -1;
-    int both = 0, r = -1, rboth = 0, rr = -1;
-#pragma unroll 8
-    for (int i = 0; i < S; ++i) {
-        const bool a = mism_w<W>(q1, (W)s1[i]) <= nsubs;
-        const bool b = mism_w<W>(q2, (W)s2[i]) <= nsubs;
-        const bool c = RC && mism_w<W>(q2, (W)s2rc[i]) <= nsubs;
-        if (a || b || c) {
-            m1 = (a && m1 < 0) ? i : m1;
-            m2 = (b && m2 < 0) ? i : m2;
-            r = (a && b && both == 0) ? i : r;
-            both += (a && b) ? 1 : 0;
-            rm2 = (c && rm2 < 0) ? i : rm2;
-            rr = (a && c && rboth == 0) ? i : rr;
-            rboth += (a && c) ? 1 : 0;
-        }
-    }
-    if (m1 >= 0 && m2 >= 0) {
-        cls = both == 0 ? CLS_HOP : both == 1 ? CLS_DEMUX : CLS_AMBIG;
-        row = both == 1 ? r : -1;
-    } else {
-        cls = CLS_UNDET;
-        row = -1;
-    }
-    if (m1 >= 0 && rm2 >= 0) {
-        rcls = rboth == 0 ? CLS_HOP : rboth == 1 ? CLS_DEMUX : CLS_AMBIG;
-        rrow = rboth == 1 ? rr : -1;
-    } else {
-        rcls = CLS_UNDET;
-        rm2 = -1;
-        rrow = -1;
-    }
-    if (cls == CLS_UNDET) {  // pass A keeps matched_idx1 from the rc call (frender.py:319-323)
-        if (rcls == CLS_UNDET) m1 = -1;
-        m2 = -1;
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// classify neighbourhood maps (fr_internal.h NbrMap): a code is classified by three map probes and
-// two pair probes instead of a scan over every sheet row
-// ------------------------------------------------------------------------------------
-__host__ __device__ inline u64 nbr_binom(int n, int k) {
-    if (k < 0 || k > n) return 0;
-    u64 r = 1;
-    for (int j = 1; j <= k; ++j) r = r * (u64)(n - k + j) / (u64)j;
-    return r;
-}
-
-u64 nbr_codes_per_row(int L, int nsubs) {
-    u64 t = 0, p5 = 1;
-    for (int d = 0; d <= nsubs && d <= L; ++d, p5 *= 5) t += nbr_binom(L, d) * p5;
-    return t;
-}
-
-template <class SL>
-__device__ __forceinline__ SL* nbr_claim(SL* t, u32 mask, u64 key) {  // the table has >= 2x free slots
-    u32 h = (u32)mix64(key) & mask;
-    for (;;) {
-        const u64 prev = atomicCAS((unsigned long long*)&t[h].key, 0ull, (unsigned long long)key);
-        if (prev == 0 || prev == key) return &t[h];
-        h = (h + 1) & mask;
-    }
-}
-
-// thread per (row, neighbour index t): t ranks (d, combination of d positions, d symbols in 1..5);
-// substitutions equal to the row's own symbol are left to the smaller d that produces the same code
-__global__ void nbr_insert_kernel(const u64* __restrict__ vals, const int32_t* __restrict__ canon, int S, int L,
-                                  int nsubs, u64 T, NSlot* m, u32 mask) {
-    const u64 g = blockIdx.x * (u64)blockDim.x + threadIdx.x;
-    if (g >= (u64)S * T) return;
-    const int i = (int)(g / T);
-    u64 t = g % T;
-    if (canon[i] != i) return;  // one insertion per distinct value
-    int d = 0;
-    u64 p5 = 1;
-    for (;; ++d, p5 *= 5) {
-        const u64 nd = nbr_binom(L, d) * p5;
-        if (t < nd) break;
-        t -= nd;
-    }
-    u64 sub = t % p5, comb = t / p5;
-    u64 v = vals[i];
-    for (int k = d; k >= 1; --k) {  // colex unranking of the position set
-        int c = k - 1;
-        while (nbr_binom(c + 1, k) <= comb) ++c;
-        comb -= nbr_binom(c, k);
-        const u64 sy = sub % 5u + 1u;
-        sub /= 5u;
-        if (((v >> (3 * c)) & 7u) == sy) return;
-        v = (v & ~(7ull << (3 * c))) | (sy << (3 * c));
-    }
-    NSlot* e = nbr_claim(m, mask, v | NBR_KEY);
-    atomicMax(&e->vmin_c, ~(u32)i);
-    atomicMax(&e->vmax1, (u32)i + 1u);
-}
-
-__global__ void nbr_pair_kernel(const int32_t* __restrict__ canon, int S, int rc, PSlot* p0, u32 m0, PSlot* p1,
-                                u32 m1) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S) return;
-    const u64 a = (u64)(u32)canon[i] << 32;
-    PSlot* e = nbr_claim(p0, m0, a | (u32)canon[S + i] | NBR_KEY);
-    atomicAdd(&e->cnt, 1u);
-    atomicMax(&e->first_c, ~(u32)i);
-    if (rc) {
-        e = nbr_claim(p1, m1, a | (u32)canon[2 * S + i] | NBR_KEY);
-        atomicAdd(&e->cnt, 1u);
-        atomicMax(&e->first_c, ~(u32)i);
-    }
-}
-
-hipError_t launch_nbr_build(const SheetArgs& sh, const int32_t* canon, int nsubs, int rc, const NbrMap& nm,
-                            hipStream_t s) {
-    const u64* vals[3] = {sh.i1, sh.i2, sh.i2rc};
-    const int len[3] = {sh.L1u, sh.L2u, sh.L2u};
-    for (int l = 0; l < (rc ? 3 : 2); ++l) {
-        const u64 T = nbr_codes_per_row(len[l], nsubs);
-        const u64 n = (u64)sh.S * T;
-        hipLaunchKernelGGL(nbr_insert_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, s, vals[l], canon + l * sh.S,
-                           sh.S, len[l], nsubs, T, nm.m[l], nm.mmask[l]);
-    }
-    hipLaunchKernelGGL(nbr_pair_kernel, dim3((u32)((sh.S + 255) / 256)), dim3(256), 0, s, canon, sh.S, rc, nm.p[0],
-                       nm.pmask[0], nm.p[1], nm.pmask[1]);
-    return hipGetLastError();
-}
-
-// one map probe chain from a slot already loaded (the caller issues the first loads of several chains
-// together, so a code waits for one round trip per stage, not one per map)
-__device__ __forceinline__ int nbr_resolve(const NSlot* __restrict__ t, u32 mask, u64 key, u32 h, NSlot e) {
-    for (;;) {
-        if (e.key == key) return ~e.vmin_c == e.vmax1 - 1u ? (int)~e.vmin_c : -2;
-        if (e.key == 0) return -1;
-        h = (h + 1) & mask;
-        e = t[h];
-    }
-}
-
-// nbr_find on the idx1, idx2 and (rc) rc(idx2) maps with the three first probes in flight together
-__device__ __forceinline__ void nbr_find3(const NbrMap& nm, u64 q1, u64 q2, bool rc, int& a1, int& a2, int& a3) {
-    const u64 k1 = q1 | NBR_KEY, k2 = q2 | NBR_KEY;
-    const u32 h1 = (u32)mix64(k1) & nm.mmask[0], h2 = (u32)mix64(k2) & nm.mmask[1], h3 = (u32)mix64(k2) & nm.mmask[2];
-    const NSlot e1 = nm.m[0][h1], e2 = nm.m[1][h2];
-    const NSlot e3 = rc ? nm.m[2][h3] : NSlot{0, 0, 0};
-    a1 = nbr_resolve(nm.m[0], nm.mmask[0], k1, h1, e1);
-    a2 = nbr_resolve(nm.m[1], nm.mmask[1], k2, h2, e2);
-    a3 = rc ? nbr_resolve(nm.m[2], nm.mmask[2], k2, h3, e3) : -1;
-}
-
-__device__ __forceinline__ void pair_resolve(const PSlot* __restrict__ t, u32 mask, u64 key, u32 h, PSlot e, int& both,
-                                             int& r) {
-    for (;;) {
-        if (e.key == key) {
-            both = (int)e.cnt;
-            r = (int)~e.first_c;
-            return;
-        }
-        if (e.key == 0) return;
-        h = (h + 1) & mask;
-        e = t[h];
-    }
-}
-
-// class_pair's result from the map probes: the rows near q1 are exactly the rows holding value a1 (a
-// single distinct value), so its first row is a1 and |M1 ∩ M2| is the pair count of (a1, a2).  The two
-// pair maps' first probes are in flight together.
-__device__ __forceinline__ void class_pair_nbr(const NbrMap& nm, int a1, int a2, int a3, int& m1, int& m2, int& cls,
-                                               int& row, int& rm2, int& rcls, int& rrow) {
-    int both = 0, r = -1, rboth = 0, rr = -1;
-    const bool f0 = a1 >= 0 && a2 >= 0, f1 = a1 >= 0 && a3 >= 0;
-    const u64 pk0 = ((u64)(u32)a1 << 32) | (u32)a2 | NBR_KEY, pk1 = ((u64)(u32)a1 << 32) | (u32)a3 | NBR_KEY;
-    const u32 ph0 = (u32)mix64(pk0) & nm.pmask[0], ph1 = (u32)mix64(pk1) & nm.pmask[1];
-    const PSlot p0 = f0 ? nm.p[0][ph0] : PSlot{0, 0, 0};
-    const PSlot p1 = f1 ? nm.p[1][ph1] : PSlot{0, 0, 0};
-    if (f0) pair_resolve(nm.p[0], nm.pmask[0], pk0, ph0, p0, both, r);
-    if (f1) pair_resolve(nm.p[1], nm.pmask[1], pk1, ph1, p1, rboth, rr);
-    m1 = a1;
-    m2 = a2;
-    rm2 = a3;
-    if (m1 >= 0 && m2 >= 0) {
-        cls = both == 0 ? CLS_HOP : both == 1 ? CLS_DEMUX : CLS_AMBIG;
-        row = both == 1 ? r : -1;
-    } else {
-        cls = CLS_UNDET;
-        row = -1;
-    }
-    if (m1 >= 0 && rm2 >= 0) {
-        rcls = rboth == 0 ? CLS_HOP : rboth == 1 ? CLS_DEMUX : CLS_AMBIG;
-        rrow = rboth == 1 ? rr : -1;
-    } else {
-        rcls = CLS_UNDET;
-        rm2 = -1;
-        rrow = -1;
-    }
-    if (cls == CLS_UNDET) {  // pass A keeps matched_idx1 from the rc call (frender.py:319-323)
-        if (rcls == CLS_UNDET) m1 = -1;
-        m2 = -1;
-    }
-}
-
-// One lane per unique code.  The sheet images (u32 when every entry has <= 10 symbols, else
-// u64) and the per-name rc sums live in dynamic LDS sized to the sheet; sheets too large for it
-// are read from HBM.
-template <typename W>
-__global__ __launch_bounds__(CLS_WG) void classify_kernel(const u64* keys, const u64* counts, u64 n, SheetArgs sh,
-                                                          int nsubs, int rc, ClassOut o, NbrMap nm,
-                                                          int sheet_in_lds, int names_in_lds, u64* zero_next,
-                                                          u32 zero_n, u64* err_flag) {
-    extern __shared__ __attribute__((aligned(16))) u8 cls_lds[];
-    // the error word + rc sums of the next fr_classify (the other of two alternating blocks): zeroed here,
-    // so no call issues a memset dispatch for its own
-    for (u64 i = blockIdx.x * (u64)CLS_WG + threadIdx.x; i < zero_n; i += (u64)gridDim.x * CLS_WG) zero_next[i] = 0;
-    unsigned long long* lf = (unsigned long long*)cls_lds;
-    unsigned long long* lr = lf + (names_in_lds ? sh.n_names : 0);
-    W* s1 = (W*)(lr + (names_in_lds ? sh.n_names : 0));
-    W* s2 = s1 + sh.S;
-    W* s2rc = s2 + sh.S;
-    if (sheet_in_lds) {
-        for (int i = threadIdx.x; i < sh.S; i += CLS_WG) {
-            s1[i] = (W)sh.i1[i];
-            s2[i] = (W)sh.i2[i];
-            s2rc[i] = rc ? (W)sh.i2rc[i] : (W)0;
-        }
-    }
-    if (rc && names_in_lds)
-        for (int i = threadIdx.x; i < sh.n_names; i += CLS_WG) lf[i] = lr[i] = 0;
-    __syncthreads();
-    // sheets outside LDS: W is u64 then (the launcher guarantees it)
-    const W* S1 = sheet_in_lds ? s1 : (const W*)sh.i1;
-    const W* S2 = sheet_in_lds ? s2 : (const W*)sh.i2;
-    const W* S2rc = sheet_in_lds ? s2rc : (const W*)sh.i2rc;
-
-    bool any_err = false;
-    // grid-stride: the per-name sums stay in LDS over many codes (one flush per workgroup: the
-    // flush's atomics all land on the same 2 x names addresses)
-    for (u64 u = blockIdx.x * (u64)CLS_WG + threadIdx.x; u < n; u += (u64)gridDim.x * CLS_WG) {
-        const u64 key = keys[u];
-        // split the code at '+': idx1, idx2 = code.split("+")[0:2]  (frender.py:306), both case-folded
-        // and packed 3 bits per letter (a1 c2 g3 t4 n5) like the sheet
-        int n1 = 0, n2 = 0;
-        bool plus = false;
-        u64 q1 = 0, q2 = 0;
-        if (key & WIDE_BIT) {  // wide key (fr_internal.h): base-5 letters, '+' position in bits 57-61
-            const u64 V = key & ((1ull << 57) - 1ull);
-            const int pp = (int)((key >> 57) & 31u);
-            int nl = 0;
-            u64 off = 0, pw = 1;
-            while (nl < WIDE_MAXN && off + pw <= V) {  // off = (5^nl - 1) / 4
-                off += pw;
-                pw *= 5;
-                ++nl;
-            }
-            u64 D = V - off;
-            plus = pp != WIDE_NOPLUS;
-            n1 = plus ? pp : nl;
-            n2 = plus ? nl - pp : 0;
-            for (int i = 0; i < nl; ++i) {
-                const u64 sy = D % 5u + 1u;
-                D /= 5u;
-                if (i < n1) q1 |= sy << (3 * i);
-                else q2 |= sy << (3 * (i - n1));
-            }
-        } else {  // fast key: symbols A1 C2 G3 T4 N5 '+'6, folded they equal the sheet's a1..n5
-            // SWAR over the 21 3-bit groups: len = symbols before the first empty group; the '+'
-            // groups (== 6) among them give p1, p2 (no per-symbol loop)
-            constexpr u64 G0 = 0x1249249249249249ull & ((1ull << 63) - 1ull);  // bit 0 of each group
-            const u64 nz = (key | (key >> 1) | (key >> 2)) & G0;                // groups holding a symbol
-            const u64 empty = ~nz & G0;
-            const int len = empty ? (int)(__builtin_ctzll(empty) / 3) : MAXSYM;
-            const u64 x = key ^ (G0 * 6ull);                                    // '+' groups become 0
-            u64 pm = ~(x | (x >> 1) | (x >> 2)) & G0;
-            pm &= len < MAXSYM ? (1ull << (3 * len)) - 1ull : ~0ull;
-            const int p1 = pm ? (int)(__builtin_ctzll(pm) / 3) : -1;
-            pm &= pm - 1ull;
-            const int p2 = pm ? (int)(__builtin_ctzll(pm) / 3) : MAXSYM;
-            plus = p1 >= 0;
-            if (plus) {
-                n1 = p1;
-                const int e2 = p2 < len ? p2 : len;
-                n2 = e2 - p1 - 1;
-                q1 = n1 ? (key & ((1ull << (3 * n1)) - 1ull)) : 0ull;
-                q2 = n2 ? ((key >> (3 * (p1 + 1))) & ((1ull << (3 * n2)) - 1ull)) : 0ull;
-            }
-        }
-        int err = 0;
-        int m1 = -1, m2 = -1, cls = CLS_UNDET, row = -1;
-        int rm2 = -1, rcls = CLS_UNDET, rrow = -1;
-        if (!plus) {
-            err = 3;
-        } else {
-            // the length asserts (frender.py:227-229), idx1 list first
-            if (sh.S > 0 && (sh.L1u == -2 || sh.L1u != n1)) err = 1;
-            else if (sh.S > 0 && (sh.L2u == -2 || sh.L2u != n2)) err = 2;
-            else {
-                int a1 = -2, a2 = -2, a3 = -1;
-                if (nm.on) nbr_find3(nm, q1, q2, rc != 0, a1, a2, a3);
-                if (a1 != -2 && a2 != -2 && a3 != -2)
-                    class_pair_nbr(nm, a1, a2, a3, m1, m2, cls, row, rm2, rcls, rrow);
-                else if (FR_CLS_SCALAR && rc)
-                    class_pair_s<W, true>((W)q1, (W)q2, sh.i1, sh.i2, sh.i2rc, sh.S, nsubs, m1, m2, cls, row, rm2,
-                                          rcls, rrow);
-                else if (FR_CLS_SCALAR)
-                    class_pair_s<W, false>((W)q1, (W)q2, sh.i1, sh.i2, sh.i2rc, sh.S, nsubs, m1, m2, cls, row, rm2,
-                                           rcls, rrow);
-                else
-                    class_pair<W>((W)q1, (W)q2, S1, S2, S2rc, sh.S, nsubs, rc != 0, m1, m2, cls, row, rm2, rcls, rrow);
-                // both calls demuxable to different sample NAMES -> ambiguous (frender.py:336-349)
-                if (rc && cls == CLS_DEMUX && rcls == CLS_DEMUX && sh.name[row] != sh.name[rrow]) {
-                    cls = CLS_AMBIG;
-                    row = -1;
-                    rcls = CLS_AMBIG;
-                    rrow = -1;
-                }
-            }
-        }
-        if (err) {
-            any_err = true;
-            atomicMax((unsigned long long*)o.err_first, (unsigned long long)~u);  // = min u
-            if (o.err_which) o.err_which[u] = err;
-        } else if (o.err_which) {
-            o.err_which[u] = 0;
-        }
-        o.m1[u] = (int16_t)m1;
-        o.m2[u] = (int16_t)m2;
-        o.cls[u] = (u8)cls;
-        o.row[u] = (int16_t)row;
-        if (rc) {
-            o.rc_m2[u] = (int16_t)rm2;
-            o.rc_cls[u] = (u8)rcls;
-            o.rc_row[u] = (int16_t)rrow;
-            // the record count only where a sum takes it (most codes are hops or undetermined)
-            const u64 cnt = (cls == CLS_DEMUX || rcls == CLS_DEMUX) ? counts[u] : 0ull;
-            if (cls == CLS_DEMUX) {
-                const int nm = sh.name[row];
-                if (names_in_lds) atomicAdd(&lf[nm], (unsigned long long)cnt);
-                else atomicAdd((unsigned long long*)&o.rc_f[nm], (unsigned long long)cnt);
-            }
-            if (rcls == CLS_DEMUX) {
-                const int nm = sh.name[rrow];
-                if (names_in_lds) atomicAdd(&lr[nm], (unsigned long long)cnt);
-                else atomicAdd((unsigned long long*)&o.rc_r[nm], (unsigned long long)cnt);
-            }
-        }
-    }
-    // pinned host memory (every lane that met an error stores the same value to the one address, once, after
-    // its loop): the host reads the exact error word, kept by the atomicMax above, only when the flag is set
-    if (any_err) *err_flag = 1;
-    if (rc && names_in_lds) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < sh.n_names; i += CLS_WG) {
-            if (lf[i]) atomicAdd((unsigned long long*)&o.rc_f[i], lf[i]);
-            if (lr[i]) atomicAdd((unsigned long long*)&o.rc_r[i], lr[i]);
-        }
-    }
-}
-
-hipError_t launch_classify(const u64* keys, const u64* counts, u64 n, SheetArgs sh, int nsubs, int rc, ClassOut o,
-                           const NbrMap& nm, u64* zero_next, u32 zero_n, u64* err_flag, hipStream_t s) {
-    // (no codes: one workgroup still zeroes the next call's block)
-    // u32 images when every sheet entry (and so every matching query) has <= 10 symbols
-    const bool narrow = sh.S > 0 && sh.L1u >= 0 && sh.L1u <= 10 && sh.L2u >= 0 && sh.L2u <= 10;
-    const size_t wb = narrow ? 4 : 8;
-    const size_t names_bytes = rc ? 2ull * 8 * sh.n_names : 0;
-    const size_t sheet_bytes = 3 * wb * (size_t)std::max(sh.S, 0);
-    const int names_in_lds = (rc && names_bytes <= CLS_LDS_BYTES / 2) ? 1 : 0;
-    const size_t nb = names_in_lds ? names_bytes : 0;
-    // the scalar-load path (FR_CLS_SCALAR) reads the rows from HBM; only the name sums use LDS then
-    const int sheet_in_lds = (!FR_CLS_SCALAR && nb + sheet_bytes <= CLS_LDS_BYTES) ? 1 : 0;
-    const size_t lds = nb + (sheet_in_lds ? sheet_bytes : 0) + 16;
-    const u64 grid = std::max<u64>(1, std::min<u64>((n + CLS_WG - 1) / CLS_WG, 2048));
-    const bool wide = !(narrow && (sheet_in_lds || FR_CLS_SCALAR));
-    if (!wide)
-        hipLaunchKernelGGL(classify_kernel<u32>, dim3((u32)grid), dim3(CLS_WG), lds, s, keys, counts, n, sh, nsubs, rc,
-                           o, nm, sheet_in_lds, names_in_lds, zero_next, zero_n, err_flag);
-    else
-        hipLaunchKernelGGL(classify_kernel<u64>, dim3((u32)grid), dim3(CLS_WG), lds, s, keys, counts, n, sh, nsubs, rc,
-                           o, nm, sheet_in_lds, names_in_lds, zero_next, zero_n, err_flag);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// demux key mode (fr_dmx_set_sheet): one lane per R2 record of a window, classified from its fast key as
-// classify_kernel classifies a unique code without rc, and turned into the record's destination at once.
-// No LDS: a code takes the three map probes; the exact row scan behind them (maps off, or a code near
-// several distinct sheet values) reads the rows by scalar loads with a uniform row index
-// (class_pair_s), so a sheet of any size takes the same path and registers alone bound the occupancy.
-// ------------------------------------------------------------------------------------
-// classify_kernel's per-key steps as helpers.  (classify_kernel keeps its own inline text: calling these from
-// it cost one more VGPR per lane in both instantiations, 51 -> 52 and 57 -> 58.)
-// A fast key (symbols A1 C2 G3 T4 N5 '+'6, folded they equal the sheet's a1..n5) split at '+' like
-// idx1, idx2 = code.split("+")[0:2] (frender.py:306): false without a '+'.
-__device__ __forceinline__ bool split_fast_key(u64 key, int& n1, int& n2, u64& q1, u64& q2) {
-    // SWAR over the 21 3-bit groups: len = symbols before the first empty group; the '+'
-    // groups (== 6) among them give p1, p2 (no per-symbol loop)
-    constexpr u64 G0 = 0x1249249249249249ull & ((1ull << 63) - 1ull);  // bit 0 of each group
-    const u64 nz = (key | (key >> 1) | (key >> 2)) & G0;                // groups holding a symbol
-    const u64 empty = ~nz & G0;
-    const int len = empty ? (int)(__builtin_ctzll(empty) / 3) : MAXSYM;
-    const u64 x = key ^ (G0 * 6ull);                                    // '+' groups become 0
-    u64 pm = ~(x | (x >> 1) | (x >> 2)) & G0;
-    pm &= len < MAXSYM ? (1ull << (3 * len)) - 1ull : ~0ull;
-    const int p1 = pm ? (int)(__builtin_ctzll(pm) / 3) : -1;
-    pm &= pm - 1ull;
-    const int p2 = pm ? (int)(__builtin_ctzll(pm) / 3) : MAXSYM;
-    const bool plus = p1 >= 0;
-    if (plus) {
-        n1 = p1;
-        const int e2 = p2 < len ? p2 : len;
-        n2 = e2 - p1 - 1;
-        q1 = n1 ? (key & ((1ull << (3 * n1)) - 1ull)) : 0ull;
-        q2 = n2 ? ((key >> (3 * (p1 + 1))) & ((1ull << (3 * n2)) - 1ull)) : 0ull;
-    }
-    return plus;
-}
-
-// the length asserts (frender.py:227-229), idx1 list first: 1 idx1, 2 idx2, 0 none
-__device__ __forceinline__ int length_error(const SheetArgs& sh, int n1, int n2) {
-    if (sh.S > 0 && (sh.L1u == -2 || sh.L1u != n1)) return 1;
-    if (sh.S > 0 && (sh.L2u == -2 || sh.L2u != n2)) return 2;
-    return 0;
-}
-
-template <typename W>
-__global__ __launch_bounds__(CLS_WG) void dmx_class_kernel(const u64* __restrict__ rec_key, int32_t* rec_dest, u64 n,
-                                                           SheetArgs sh, int nsubs, NbrMap nm,
-                                                           const int32_t* __restrict__ row_dest, DmxClassDest cd) {
-    for (u64 u = blockIdx.x * (u64)CLS_WG + threadIdx.x; u < n; u += (u64)gridDim.x * CLS_WG) {
-        if (rec_dest[u] != DMX_PENDING) continue;  // exotic: the host resolves it
-        int n1 = 0, n2 = 0;
-        u64 q1 = 0, q2 = 0;
-        int32_t d;
-        if (!split_fast_key(rec_key[u], n1, n2, q1, q2)) {
-            d = FR_DMX_NOPLUS;
-        } else if (const int err = length_error(sh, n1, n2)) {
-            d = err == 1 ? FR_DMX_LEN1 : FR_DMX_LEN2;
-        } else {
-            int m1, m2, cls, row, rm2, rcls, rrow;
-            int a1 = -2, a2 = -2, a3 = -1;
-            if (nm.on) nbr_find3(nm, q1, q2, false, a1, a2, a3);
-            if (a1 != -2 && a2 != -2) class_pair_nbr(nm, a1, a2, a3, m1, m2, cls, row, rm2, rcls, rrow);
-            else class_pair_s<W, false>((W)q1, (W)q2, sh.i1, sh.i2, sh.i2rc, sh.S, nsubs, m1, m2, cls, row, rm2, rcls,
-                                        rrow);
-            d = cls == CLS_DEMUX ? row_dest[row] : cls == CLS_HOP ? cd.v[CLS_HOP] : cls == CLS_AMBIG ? cd.v[CLS_AMBIG]
-                                                                                                     : cd.v[CLS_UNDET];
-        }
-        rec_dest[u] = d;
-    }
-}
-
-hipError_t launch_dmx_classify(const u64* rec_key, int32_t* rec_dest, u64 n, SheetArgs sh, int nsubs,
-                               const NbrMap& nm, const int32_t* row_dest, DmxClassDest cd, hipStream_t s) {
-    if (!n) return hipSuccess;
-    // u32 distances when every sheet entry (and so every query that passes the length checks) has <= 10 symbols
-    const bool narrow = sh.S > 0 && sh.L1u >= 0 && sh.L1u <= 10 && sh.L2u >= 0 && sh.L2u <= 10;
-    const u64 grid = std::max<u64>(1, std::min<u64>((n + CLS_WG - 1) / CLS_WG, 2048));
-    if (narrow)
-        hipLaunchKernelGGL(dmx_class_kernel<u32>, dim3((u32)grid), dim3(CLS_WG), 0, s, rec_key, rec_dest, n, sh, nsubs,
-                           nm, row_dest, cd);
-    else
-        hipLaunchKernelGGL(dmx_class_kernel<u64>, dim3((u32)grid), dim3(CLS_WG), 0, s, rec_key, rec_dest, n, sh, nsubs,
-                           nm, row_dest, cd);
-    return hipGetLastError();
-}
-
-// generic classifier over case-folded code points (codes outside the fast alphabet)
-__device__ void class_of_cp(const u32* q1, int n1, const u32* q2, int n2, const u32* s1, const u32* s2, int stride,
-                            int S, int nsubs, int& m1, int& m2, int& cls, int& row) {
-    m1 = -1;
-    m2 = -1;
-    int both = 0, r = -1;
-    for (int i = 0; i < S; ++i) {
-        int d1 = 0, d2 = 0;
-        for (int k = 0; k < n1; ++k) d1 += q1[k] != s1[(u64)i * stride + k];
-        for (int k = 0; k < n2; ++k) d2 += q2[k] != s2[(u64)i * stride + k];
-        const bool a = d1 <= nsubs, b = d2 <= nsubs;
-        if (a && m1 < 0) m1 = i;
-        if (b && m2 < 0) m2 = i;
-        if (a && b) {
-            if (!both) r = i;
-            ++both;
-        }
-    }
-    if (m1 >= 0 && m2 >= 0) {
-        cls = both == 0 ? CLS_HOP : both == 1 ? CLS_DEMUX : CLS_AMBIG;
-        row = both == 1 ? r : -1;
-    } else {
-        cls = CLS_UNDET;
-        m1 = m2 = row = -1;
-    }
-}
-
-__global__ void classify_cp_kernel(int n, const u32* q1, const int32_t* q1len, const u32* q2, const int32_t* q2len,
-                                   int stride, int S, const u32* s1, const int32_t* s1len, const u32* s2,
-                                   const int32_t* s2len, const u32* s2rc, const int32_t* name, int nsubs, int rc,
-                                   ClassOut o) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n) return;
-    const int n1 = q1len[u], n2 = q2len[u];
-    int err = 0;
-    for (int i = 0; i < S && !err; ++i)
-        if (s1len[i] != n1) err = 1;
-    for (int i = 0; i < S && !err; ++i)
-        if (s2len[i] != n2) err = 2;
-    int m1 = -1, m2 = -1, cls = CLS_UNDET, row = -1, rm2 = -1, rcls = CLS_UNDET, rrow = -1;
-    if (!err) {
-        class_of_cp(q1 + (u64)u * stride, n1, q2 + (u64)u * stride, n2, s1, s2, stride, S, nsubs, m1, m2, cls, row);
-        if (rc) {
-            int rm1;
-            class_of_cp(q1 + (u64)u * stride, n1, q2 + (u64)u * stride, n2, s1, s2rc, stride, S, nsubs, rm1, rm2,
-                        rcls, rrow);
-            if (cls == CLS_UNDET && rcls != CLS_UNDET) m1 = rm1;  // matched_idx1 of pass A (frender.py:319-323)
-            if (cls == CLS_DEMUX && rcls == CLS_DEMUX && name[row] != name[rrow]) {
-                cls = rcls = CLS_AMBIG;
-                row = rrow = -1;
-            }
-        }
-    }
-    if (o.err_which) o.err_which[u] = err;
-    o.m1[u] = (int16_t)m1;
-    o.m2[u] = (int16_t)m2;
-    o.cls[u] = (u8)cls;
-    o.row[u] = (int16_t)row;
-    if (rc) {
-        o.rc_m2[u] = (int16_t)rm2;
-        o.rc_cls[u] = (u8)rcls;
-        o.rc_row[u] = (int16_t)rrow;
-    }
-}
-
-hipError_t launch_classify_cp(int n, const u32* q1, const int32_t* q1len, const u32* q2, const int32_t* q2len,
-                              int stride, int S, const u32* s1, const int32_t* s1len, const u32* s2,
-                              const int32_t* s2len, const u32* s2rc, const int32_t* name, int nsubs, int rc,
-                              ClassOut o, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(classify_cp_kernel, dim3((n + 127) / 128), dim3(128), 0, s, n, q1, q1len, q2, q2len, stride,
-                       S, s1, s1len, s2, s2len, s2rc, name, nsubs, rc, o);
     return hipGetLastError();
 }
 

@@ -366,6 +366,158 @@ def test_classify_random(ctx, lib, nsubs, rc):
         assert r.tolist() == [r_exp[n] for n in names]
 
 
+def _feed_codes(c, lib, codes, reps=None):
+    """Tally one record per code (reps[j] records of code j) -> the table holds codes in this order."""
+    data = "".join(f"@r{i} 1:N:0:{code}\n\n+\n\n" * (reps[i] if reps else 1) for i, code in enumerate(codes)).encode()
+    c.reset()
+    c.begin_file(None)
+    c.feed(data)
+    c.end_file()
+    c.finalize()
+    keys, counts, _ = c.unique()
+    assert lib.decode_keys(keys) == codes
+    return counts
+
+
+_RC_SUM_CASES = {}
+
+
+def _rc_sum_case(n_names):
+    """An 8+8 sheet of n_names rows with distinct names, 200 codes around it with their record counts, and
+    the oracle's result per code and (f, r) sums per name, weighted by count (computed once per sheet)."""
+    if n_names in _RC_SUM_CASES:
+        return _RC_SUM_CASES[n_names]
+    from frender_amd.host import reverse_complement
+    from oracle.frender_oracle import classify_code
+    rng = random.Random(n_names)
+
+    def draw():
+        return ["".join("ACGT"[(v >> (2 * k)) & 3] for k in range(8)) for v in rng.sample(range(4 ** 8), n_names)]
+    idx1, idx2 = draw(), draw()
+    ids = [f"n{i}" for i in range(n_names)]
+    codes = []
+    for _ in range(200):  # (the oracle walks every row four times per code: 300 codes took it 4 s)
+        s = rng.randrange(n_names)
+        a = list(idx1[s])
+        b = list(idx2[rng.randrange(n_names)] if rng.random() < 0.3 else idx2[s])
+        if rng.random() < 0.2:
+            b = list(reverse_complement("".join(b)))
+        for arr in (a, b):
+            for _ in range(rng.randint(0, 3)):
+                arr[rng.randrange(8)] = rng.choice("ACGTN")
+        codes.append("".join(a) + "+" + "".join(b))
+    codes = list(dict.fromkeys(codes))
+    reps = [rng.choice((1, 1, 2, 3)) for _ in codes]
+    exp = [classify_code(code, n, idx1, idx2, ids, 1, True) for code, n in zip(codes, reps)]
+    f_exp = {n: 0 for n in ids}
+    r_exp = {n: 0 for n in ids}
+    for e, n in zip(exp, reps):
+        if e["sample_name"]:
+            f_exp[e["sample_name"]] += n
+        if e["rc_sample_name"]:
+            r_exp[e["rc_sample_name"]] += n
+    case = (idx1, idx2, ids, codes, reps, exp, [f_exp[n] for n in ids], [r_exp[n] for n in ids])
+    _RC_SUM_CASES[n_names] = case
+    return case
+
+
+@pytest.mark.parametrize("nbr", [1, 0])
+@pytest.mark.parametrize("n_names", [1536, 1537])
+def test_classify_rc_sums_at_lds_bound(lib, n_names, nbr):
+    """The per-name rc sums on either side of the bound of their LDS copy: 1536 names are the last sheet whose
+    two u64 sums per name fit half the classifier's dynamic LDS (16 * n_names <= 24576), 1537 the first
+    that adds to the global sums directly.  Through the maps and (nbr = 0) through the row scan; codes fed
+    one to three times, so the sums are weighted by record count."""
+    from frender_amd.host import reverse_complement
+    from frender_amd.scan import _sheet_names
+    idx1, idx2, ids, codes, reps, exp, f_exp, r_exp = _rc_sum_case(n_names)
+    idx2rc = [reverse_complement(x) for x in idx2]
+    names, nid = _sheet_names(ids)
+    assert names == ids
+    c = lib.Context(device=0, chunk_bytes=1 << 20, table_slots=1 << 16, tuning={"nbr": nbr})
+    try:
+        counts = _feed_codes(c, lib, codes, reps)
+        assert counts.tolist() == reps
+        c.set_sheet(idx1, idx2, idx2rc, nid, len(names))
+        out = c.classify(1, True)
+        assert out["err_unique"] == -1
+        for j, (code, e) in enumerate(zip(codes, exp)):
+            assert lib.CLASS_NAMES[out["cls"][j]] == e["read_type"], (code, e)
+            assert (ids[out["row"][j]] if out["row"][j] >= 0 else "") == e["sample_name"], (code, e)
+            assert lib.CLASS_NAMES[out["rc_cls"][j]] == e["rc_read_type"], (code, e)
+            assert (ids[out["rc_row"][j]] if out["rc_row"][j] >= 0 else "") == e["rc_sample_name"], (code, e)
+        f, r = c.rc_counts()
+        assert sum(f_exp) > 0 and sum(r_exp) > 0
+        assert f.tolist() == f_exp
+        assert r.tolist() == r_exp
+    finally:
+        c.close()
+
+
+def _error_word_codes():
+    from frender_amd import synth
+    rng = random.Random(77)
+    sheet = synth.make_sheet(24, 8, 8, seed=5)
+    codes = []
+    while len(codes) < 600:  # more than two 256-lane workgroups, all 8+8
+        s = rng.randrange(24)
+        a, b = list(sheet.idx1[s]), list(sheet.idx2[rng.randrange(24)])
+        for arr in (a, b):
+            for _ in range(rng.randint(0, 3)):
+                arr[rng.randrange(8)] = rng.choice("ACGTN")
+        code = "".join(a) + "+" + "".join(b)
+        if code not in codes:
+            codes.append(code)
+    return sheet, codes
+
+
+@pytest.mark.parametrize("offender,which", [("ACGTACGTTTGCATGC", 3),            # no '+'
+                                            ("ACGTACG+ACGTACGT", 1),            # 7+8
+                                            ("ACGTACGT+ACGTACG", 2),            # 8+7
+                                            ("ACGTACGTACGT+TTGCATGCATGC", 1),   # 12+12: a wide key
+                                            ("ACGTACG+ACGTACG", 1)])            # 7+7: the idx1 list first
+def test_classify_error_word(ctx, lib, offender, which):
+    """The error word: the smallest table index of a code with an error (the atomicMax of ~index) and which
+    assert it fails, with a second, different offender behind it in another workgroup; and the next classify,
+    on a clean table, reports none (the launch before it zeroed its alternating error block)."""
+    from frender_amd.host import reverse_complement
+    from frender_amd.scan import _sheet_names
+    sheet, clean = _error_word_codes()
+    k, k2 = 300, 580
+    second = "ACGTACGT+ACGTA" if which != 2 else "ACGTACGTAACC"
+    codes = clean[:k] + [offender] + clean[k:k2] + [second] + clean[k2:]
+    assert codes[k] == offender and codes.index(second) > k + 256
+    names, nid = _sheet_names(list(sheet.ids))
+    idx2rc = [reverse_complement(x) for x in sheet.idx2]
+    for rc in (False, True):
+        _feed_codes(ctx, lib, codes)
+        ctx.set_sheet(list(sheet.idx1), list(sheet.idx2), idx2rc, nid, len(names))
+        out = ctx.classify(1, rc)
+        assert (out["err_unique"], out["err_which"]) == (k, which)
+        _feed_codes(ctx, lib, clean)
+        out = ctx.classify(1, rc)
+        assert (out["err_unique"], out["err_which"]) == (-1, 0)
+        assert len(set(out["cls"].tolist())) > 1  # and it classified
+
+
+def test_classify_empty_sheet(ctx, lib):
+    """A sheet without rows raises no length error (both asserts need a row) and leaves every code with a '+'
+    undetermined, whatever its lengths; a code without '+' is still error 3."""
+    _, clean = _error_word_codes()
+    codes = clean[:300] + ["ACGTACG+ACGTA", "ACGTACGTACGT+TTGCATGCATGC"] + clean[300:]
+    ctx.set_sheet([], [], [], [], 0)
+    _feed_codes(ctx, lib, codes)
+    out = ctx.classify(1, False)
+    assert (out["err_unique"], out["err_which"]) == (-1, 0)
+    for k in ("m1", "m2", "row"):
+        assert set(out[k].tolist()) == {-1}
+    assert set(out["cls"].tolist()) == {0}
+    assert lib.CLASS_NAMES[0] == "undetermined"
+    _feed_codes(ctx, lib, codes + ["ACGTACGT"])
+    out = ctx.classify(1, False)
+    assert (out["err_unique"], out["err_which"]) == (len(codes), 3)
+
+
 @pytest.mark.parametrize("nsubs", [0, 1, 2, 3])
 @pytest.mark.parametrize("rc", [False, True])
 def test_classify_neighbourhood_maps(lib, nsubs, rc):
