@@ -52,13 +52,8 @@ struct fr_ctx {
     u64* cold = nullptr;
     u32 cold_cap = 8192;
     // launch log (fr_internal.h LogEntry): commits append, launch_log_aggregate folds it into the table
-    LogEntry* log = nullptr;
-    u64 log_cap = 0;
-    u32 log_rcap = 0;              // entries per log region (LOG_NR regions)
-    LogEntry* log_sub = nullptr;   // the split pass's sub-region parts (LOG_NSUB x log_scap)
-    u32 log_scap = 0;
-    void* log_temp = nullptr;
-    size_t log_temp_bytes = 0;
+    LogEntry* log = nullptr;       // LOG_NSUB parts of log_scap entries (nullptr: fr_tuning::log = 0)
+    u32 log_scap = 0;              // entries per part
     u32 log_min = 0;               // pairs from which a commit logs (round 6: every commit.  Direct commits are bound by
                                    // the memory-side atomics, ~23.7 G/s chip-wide whatever their scope or footprint:
                                    // scripts/ubench_l2atomic.hip; config 2's ~12M per 100M reads cost 0.4 ms)
@@ -116,9 +111,9 @@ struct fr_ctx {
     u64 feed_keys = ~0ull;    // codes the last device feed created (a range over RANGE_FIRST_MAX needs table room for them)
     bool feed_logged = true;  // the last device feed's commits went to the launch log: its ranges stay <= RANGE_FIRST_MAX
                               // unless its folds had room (one aggregation over a bigger range has more distinct codes
-                              // per sub-region than log_reduce_kernel's LDS fold holds: measured 15 ms instead of 0.28
-                              // per launch at the config-3 shape)
-    u32 feed_fold_max = 0;    // the last device feed's fullest sub-region fold, its fold overflows and range size:
+                              // per part of the log than log_reduce_kernel's LDS fold holds: measured 15 ms instead of
+                              // 0.28 per launch at the config-3 shape)
+    u32 feed_fold_max = 0;    // the last device feed's fullest fold of a part, its fold overflows and range size:
     u32 feed_fold_over = 0;   // a logged feed's next ranges may exceed RANGE_FIRST_MAX when the folds, scaled by the
     u64 feed_step = 0;        // range size, stay at most 0.85 full
     u32 chunk_tiles = 320;  // wave-tiles (4 KiB) per full chunk of a ramped launch (FR_CHUNK_TILES; round 2's
@@ -316,7 +311,7 @@ static int grow_table(fr_ctx* ctx, bool force_bigger) {
         Table t = ctx->tab;
         t.slots = ns_slots;
         t.mask = ns - 1;
-        CK(launch_rehash(t, ctx->st, ctx->tab.slots, ctx->nslots, ctx->stream));
+        CK(launch_rehash(t, ctx->tab.slots, ctx->nslots, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         CK(hipFree(ctx->tab.slots));
         ctx->tab = t;
@@ -649,10 +644,9 @@ static int launch_range(fr_ctx* ctx, const u8* dptr, u64 len, u64 avail, int own
     a.cold = ctx->cold;
     // launch-log first occurrences fold in 32 bits (4-B ordinals: ranges up to RANGE_MAX); one aggregation's
     // distinct codes must fit its LDS fold, which fr_feed_device's range size sees to
-    // (direct logging: the commits append to the sub-region parts, log_scap entries each)
-    a.log = exo_only ? nullptr : LOG_DIRECT ? ctx->log_sub : ctx->log;
-    a.log_cap = LOG_DIRECT ? (u64)ctx->log_scap * LOG_NSUB : ctx->log_cap;
-    a.log_rcap = LOG_DIRECT ? ctx->log_scap : ctx->log_rcap;
+    a.log = exo_only ? nullptr : ctx->log;
+    a.log_cap = (u64)ctx->log_scap * LOG_NSUB;
+    a.log_scap = ctx->log_scap;
     a.log_min = ctx->log_min;
     a.log_hot = ctx->log_hot;
     a.rare = ctx->rare;
@@ -666,8 +660,8 @@ static int launch_range(fr_ctx* ctx, const u8* dptr, u64 len, u64 avail, int own
     if (timed) CK(hipEventRecord(ctx->ev_b[ctx->ev_used], ctx->stream));
     const bool mir = mirror && a.log;
     if (a.log) {
-        CK(launch_log_aggregate(ctx->tab, ctx->st, ctx->log, ctx->log_rcap, ctx->log_sub, ctx->log_scap, a.file_tag,
-                                a.file_offset, mir ? ctx->d_mir : nullptr, mir ? dptr + len - 1 : nullptr, ctx->stream));
+        CK(launch_log_aggregate(ctx->tab, ctx->st, ctx->log, ctx->log_scap, a.file_tag, a.file_offset,
+                                mir ? ctx->d_mir : nullptr, mir ? dptr + len - 1 : nullptr, ctx->stream));
         ctx->fold_zero = false;
     }
     if (timed) {
@@ -759,15 +753,11 @@ fr_ctx* fr_create_tuned(int device, uint64_t chunk_bytes, uint64_t table_slots, 
     // that does not fit inserts into the table directly).  Only heavy commits log (ScanArgs::log_min);
     // fr_tuning::log = 0 turns the log off
     if (t.log) {
-        // entries: 1 per 256 B of a launch (SYN-v1 config 3 logs ~1 per 700 B), in LOG_NR equal regions;
-        // a run past its region's end inserts directly
+        // entries: 1 per 256 B of a launch (SYN-v1 config 3 logs ~1 per 700 B); each of the LOG_NSUB parts gets
+        // twice its mean share of them (the parts fill unevenly), and a pair past its part's end inserts directly
         const u64 want = std::min<u64>(std::max<u64>(ctx->chunk_bytes / 256, 1ull << 16), 1ull << 26);
-        ctx->log_rcap = (u32)(want / LOG_NR);
-        ctx->log_cap = (u64)ctx->log_rcap * LOG_NR;
-        ctx->log_scap = (u32)std::max<u64>(2ull * ctx->log_rcap / LOG_SUBS, 64);  // 2x the mean share
-        // (direct logging: the commits fill the sub-region parts, no region parts)
-        if (!LOG_DIRECT && (e = dalloc(&ctx->log, ctx->log_cap)) != hipSuccess) return bad("launch log", e);
-        if ((e = dalloc(&ctx->log_sub, (u64)ctx->log_scap * LOG_NSUB)) != hipSuccess) return bad("launch log parts", e);
+        ctx->log_scap = (u32)std::max<u64>(2ull * want / LOG_NSUB, 64);
+        if ((e = dalloc(&ctx->log, (u64)ctx->log_scap * LOG_NSUB)) != hipSuccess) return bad("launch log", e);
     }
     ctx->tiles_cap = RANGE_MAX / TSTEP + 2;
     ctx->nslots = pow2_at_least(std::max<u64>(table_slots, 1024));
@@ -834,8 +824,7 @@ void fr_destroy(fr_ctx* ctx) {
                    ctx->d_keys, ctx->d_counts, ctx->d_first, ctx->d_keys_s, ctx->d_counts_s,
                    ctx->d_first_s, ctx->d_pos, ctx->d_perm, ctx->d_rank, ctx->d_counter, ctx->d_temp, ctx->d_bins, ctx->d_binbase, ctx->d_arr, ctx->d_rows, ctx->d_pres_u,
                    ctx->d_pres_f, ctx->d_pres_c, ctx->d_m1, ctx->d_m2, ctx->d_row, ctx->d_rm2, ctx->d_rrow, ctx->d_cls, ctx->d_rcls,
-                   ctx->d_errw, ctx->d_errf, ctx->d_nbr, ctx->cold, ctx->rare, ctx->chunk_info, ctx->log, ctx->log_sub, ctx->log_temp,
-                   ctx->snap};
+                   ctx->d_errw, ctx->d_errf, ctx->d_nbr, ctx->cold, ctx->rare, ctx->chunk_info, ctx->log, ctx->snap};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     if (ctx->h_st) (void)hipHostFree(ctx->h_st);
@@ -1511,7 +1500,7 @@ int fr_finalize(fr_ctx* ctx, uint64_t* n_unique, uint64_t* n_presence, uint64_t*
                             end_bit, ctx->stream));
         CK(launch_gather(ctx->d_perm, nk, ctx->d_keys, ctx->d_counts, ctx->d_keys_s, ctx->d_counts_s, ctx->d_rank,
                          ctx->stream));
-        CK(launch_set_uidx(ctx->tab.slots, ctx->tab.mask, ctx->d_keys_s, nk, ctx->d_rank, ctx->stream));
+        CK(launch_set_uidx(ctx->tab.slots, ctx->tab.mask, ctx->d_keys_s, nk, ctx->stream));
     }
     const u64 np = ctx->pres_defer_tag ? nk : std::min<u64>(ctx->h_st->n_presence, ctx->tab.pres_cap);
     if (np > ctx->pmap_cap) {

@@ -1,5 +1,7 @@
-// fr_internal.h — device data layout shared by the kernels (fr_kernels.hip) and the
-// C-ABI context (fr_api.hip).  See DESIGN.md §3 for the HBM layout.
+// fr_internal.h — device data layout shared by the kernels (the tally in fr_kernels.hip, the table
+// kernels in fr_table.hip, the classifier in fr_classify.hip) and the C-ABI context (fr_api.hip).
+// Plain C++ (fr_gz.cpp includes it); device code the kernel files share is fr_table_dev.h.
+// See DESIGN.md §3 for the HBM layout.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,13 +86,13 @@ struct alignas(32) Overflow {
     u32 tag, pad;
 };
 
-// One tallied (code, count) pair on its way to the HBM table: a heavy chunk's LDS-table slots and
-// cold-list misses go to the launch log at the chunk's commit, counted in LDS by the pairs' regions
-// (log_region: the table home's top LOG_REGION_BITS bits) and appended as one run per region to that
-// region's part of the log (one cursor atomic per region and commit: runs of tens of pairs).  After
-// the launch a split pass counting-sorts every region's part by sub-region (the next LOG_SUB_BITS home
-// bits) into the sub-region parts, and one workgroup per sub-region folds its part in LDS, so the HBM
-// table sees one insert per distinct code per launch instead of one per commit and miss.
+// One tallied (code, count) pair on its way to the HBM table.  The launch log is LOG_NSUB parts of
+// ScanArgs::log_scap entries each, one per value of log_bucket (the top LOG_REGION_BITS + LOG_SUB_BITS
+// bits of the code's table home), each with a cursor in DevState::log_scur.  A logging commit counts its
+// LDS-table slots and cold-list misses per part in LDS, claims one run per part with one cursor atomic,
+// and writes the pairs there; a pair past its part's end inserts into the table directly.  After the
+// launch one workgroup per part (log_reduce_kernel, fr_table.hip) folds its part in LDS, so the HBM table
+// sees one insert per distinct code per launch instead of one per commit and miss.
 struct alignas(16) LogEntry {
     u64 key;
     u64 oc;              // min launch offset of the entry's records << LOG_CNT_BITS | records (log_pack): offsets of
@@ -107,19 +109,10 @@ __host__ __device__ inline u32 log_cnt(u64 oc) { return (u32)(oc & LOG_CNT_MAX);
 #ifndef FR_LOG_SUB_BITS
 #define FR_LOG_SUB_BITS 3
 #endif
-constexpr int LOG_REGION_BITS = FR_LOG_REGION_BITS;
-constexpr int LOG_NR = 1 << LOG_REGION_BITS;  // launch-log regions (parts of the log, one cursor each)
-constexpr int LOG_SUB_BITS = FR_LOG_SUB_BITS;
-constexpr int LOG_SUBS = 1 << LOG_SUB_BITS;   // sub-regions per region (aggregation workgroups)
-constexpr int LOG_NSUB = LOG_NR * LOG_SUBS;    // sub-regions in all
-#ifndef FR_LOG_DIRECT
-#define FR_LOG_DIRECT 1
-#endif
-// round 6: commits append straight to the sub-region parts (LOG_NSUB runs per commit, no split pass);
-// 0 = the region runs + split pass of rounds 4-5 (A/B builds)
-constexpr bool LOG_DIRECT = FR_LOG_DIRECT != 0;
-constexpr int LOG_NB = LOG_DIRECT ? LOG_NSUB : LOG_NR;  // a commit's log buckets
-constexpr int AGG_LNS = 4096;  // LDS slots of one sub-region's fold in log_reduce_kernel (64 KB: 2 workgroups per CU)
+constexpr int LOG_REGION_BITS = FR_LOG_REGION_BITS;  // the two knobs add up: the log's parts are the table's
+constexpr int LOG_SUB_BITS = FR_LOG_SUB_BITS;        // home ranges by their top LOG_REGION_BITS + LOG_SUB_BITS bits
+constexpr int LOG_NSUB = 1 << (LOG_REGION_BITS + LOG_SUB_BITS);  // parts of the launch log (one cursor, one aggregation workgroup each)
+constexpr int AGG_LNS = 4096;  // LDS slots of one part's fold in log_reduce_kernel (64 KB: 2 workgroups per CU)
 
 struct DevState {
     // per-file block (contiguous: fr_begin_file resets it with one copy from the reset image)
@@ -153,11 +146,11 @@ struct DevState {
     u32 commits_done;    // chunks of the current launch that finished their commit (back to 0 by the last)
     u32 heavy_launches;  // ramped launches since the reset that walked the heavy geometry (diagnostics)
     u64 chunks_total;    // chunks committed since the reset
-    u32 log_rcur[LOG_NR];  // per launch-log region: entries claimed this launch (the aggregation zeroes them)
-    u32 log_scur[LOG_NSUB];  // per sub-region: entries the split pass placed (the aggregation zeroes them)
+    u32 log_scur[LOG_NSUB];  // per part of the launch log: entries claimed this launch (may exceed log_scap; the
+                         // aggregation zeroes them)
     u32 log_red_done;    // aggregation workgroups finished (the last zeroes it)
-    u32 log_fold_max;    // the fullest sub-region fold (distinct codes) of the current device feed's aggregations
-    u32 log_fold_over;   // entries that found their sub-region's fold full (inserted on their own)
+    u32 log_fold_max;    // the fullest part's fold (distinct codes) of the current device feed's aggregations
+    u32 log_fold_over;   // entries that found their part's fold full (inserted on their own)
 };
 
 // The pinned, device-visible host block through which the common path's kernels report to the host
@@ -218,9 +211,11 @@ struct ScanArgs {
     u64* cold;           // chunk kernel: cold lists, [grid][cold_cap] x {key, ordinal}
     uint4* rare;         // chunk kernel: rare-event rings, [grid][RARE_RING] (fr_kernels.hip)
     u64* chunk_info;     // chunk kernel: per chunk {line count, spec flag + guessed phase << 1 in the high word}
-    LogEntry* log;       // the launch log (nullptr: commits insert into the HBM table directly)
-    u64 log_cap;         // LOG_NB x log_rcap
-    u32 log_rcap;        // entries per log bucket (a run past it inserts directly)
+    LogEntry* log;       // the launch log, LOG_NSUB x log_scap (nullptr: commits insert into the HBM table directly)
+    u64 log_cap;         // LOG_NSUB x log_scap.  No kernel reads it; it keeps its 8 bytes because without them every
+                         // later field's offset moves in the tally's code, and one of its 16-B argument loads
+                         // lands on an 8-B boundary ("Tally in a file of its own")
+    u32 log_scap;        // entries per part (a pair past it inserts directly)
     u32 log_min;         // a commit of at least log_min pairs goes to the log, smaller ones straight into the table
     u32 log_hot;         // ... except its LDS entries of at least log_hot records, which insert directly
     u32 exo_only;        // replay of a launch whose exotic list overflowed: capture exotic records only (no
@@ -301,28 +296,23 @@ __host__ __device__ inline u64 mix64(u64 x) {
     return x;
 }
 
-// launch-log region of a code: the top bits of mix64, as the table's home slot, so a region's codes
-// live in one contiguous part of a table of at least LOG_NR slots
-__host__ __device__ inline u32 log_region(u64 key) { return (u32)(mix64(key) >> (64 - LOG_REGION_BITS)); }
-// a commit's log bucket: the region, or with LOG_DIRECT the region and sub-region (region * LOG_SUBS + sub)
+// a code's part of the launch log: the top bits of mix64, as the table's home slot, so a part's codes
+// live in one contiguous range of a table of at least LOG_NSUB slots
 __host__ __device__ inline u32 log_bucket(u64 key) {
-    return (u32)(mix64(key) >> (64 - LOG_REGION_BITS - (LOG_DIRECT ? LOG_SUB_BITS : 0)));
-}
-__host__ __device__ inline u32 log_subregion(u64 key) {
-    return (u32)(mix64(key) >> (64 - LOG_REGION_BITS - LOG_SUB_BITS)) & (LOG_SUBS - 1);
+    return (u32)(mix64(key) >> (64 - LOG_REGION_BITS - LOG_SUB_BITS));
 }
 
-// ---- launchers (fr_kernels.hip; the classifier's in fr_classify.hip) --------------------------------------------------
+// ---- launchers: the tally's (launch_chunk_scan, chunk_occupancy) in fr_kernels.hip, the classifier's (launch_classify*,
+// launch_nbr_build, launch_dmx_classify) in fr_classify.hip, every other one in fr_table.hip ---------------------------
 // st != nullptr: workgroup 0 also writes the reset image of the device state (all zero, no error offset)
 hipError_t launch_table_init(GSlot* slots, u64 n, DevState* st, hipStream_t s);
 hipError_t launch_chunk_scan(const ScanArgs& a, int grid, hipStream_t s);
 int chunk_occupancy();  // tally workgroups per CU the kernel is built for
 hipError_t launch_reinsert_overflow(Table t, DevState* st, const Overflow* src, u64 n, hipStream_t s);
-hipError_t launch_rehash(Table dst, DevState* st, const GSlot* src, u64 nsrc, hipStream_t s);
+hipError_t launch_rehash(Table dst, const GSlot* src, u64 nsrc, hipStream_t s);
 hipError_t launch_compact(const GSlot* slots, u64 nslots, u64* keys, u64* counts, u64* first, u32* pos,
                           u64* counter, hipStream_t s);
-hipError_t launch_set_uidx(GSlot* slots, u64 mask, const u64* keys, u64 n, const u32* rank_of_pos,
-                           hipStream_t s);
+hipError_t launch_set_uidx(GSlot* slots, u64 mask, const u64* keys, u64 n, hipStream_t s);
 hipError_t launch_order(const u64* first_in, const u32* pos_in, u64 n, u64* first_out, u32* perm_out,
                         void* temp, size_t* temp_bytes, int begin_bit, int end_bit, hipStream_t s);
 hipError_t launch_gather(const u32* perm, u64 n, const u64* keys, const u64* counts, u64* keys_o,
@@ -384,12 +374,11 @@ hipError_t launch_merge(Table t, DevState* st, const u64* keys, const u64* count
 hipError_t launch_partition_rows(const u64* keys, const u64* counts_in, const u64* first, u64 n, u32 world,
                                  u64* counts, u64* cursor, u64* rows, hipStream_t s);
 hipError_t launch_merge_rows(Table t, DevState* st, const u64* rows, u64 n, hipStream_t s);
-// aggregate the launch log into the table and empty it (stream-ordered; reads log_n and the region
-// cursors on the device)
+// aggregate the launch log (LOG_NSUB parts of scap entries) into the table and empty it (stream-ordered; reads
+// log_n and the parts' cursors on the device)
 // mir != nullptr (a device feed's last launch): the last workgroup mirrors the state and *last_byte into it
-hipError_t launch_log_aggregate(Table t, DevState* st, const LogEntry* log, u32 rcap, LogEntry* sub, u32 scap,
-                                u32 file_tag, u64 file_offset, HostMirror* mir, const u8* last_byte, hipStream_t s);
-size_t log_aggregate_temp_bytes();
+hipError_t launch_log_aggregate(Table t, DevState* st, const LogEntry* log, u32 scap, u32 file_tag, u64 file_offset,
+                                HostMirror* mir, const u8* last_byte, hipStream_t s);
 hipError_t launch_synth(u8* out, u64 r0, u64 n, int R, u64 seed, const u8* idx1, const u8* idx2, int S, int L1,
                         int L2, hipStream_t s);
 

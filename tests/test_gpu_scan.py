@@ -169,7 +169,8 @@ def test_speculative_commit_replay(lib, log_min):
 @pytest.mark.parametrize("log_min,log_hot", [("0", 4), ("0", 1 << 30), ("60", 4), ("100000000", 4)])
 def test_launch_log_commits(lib, log_min, log_hot):
     """Commits of at least fr_tuning.log_min pairs go to the launch log and are aggregated after the launch
-    (count / scatter / LDS reduce / round-based table inserts); smaller ones insert directly.  Every
+    (one run per part of the log claimed at the commit, then one workgroup per part: LDS fold and round-based
+    table inserts); smaller ones insert directly.  Every
     commit logged (0), a mix (60: these 2-wave-tile chunks commit ~30-110 pairs), and none must give the
     oracle's tally, including a table that has to grow between launches.  log_hot 2^30 logs the hot
     codes too (every pair of every commit goes through the log)."""
@@ -190,8 +191,8 @@ def test_launch_log_commits(lib, log_min, log_hot):
 
 
 def test_launch_log_parts_full(lib):
-    """A launch whose commits log more pairs than a sub-region part holds: with chunk_bytes 16 MiB the log
-    has its minimum of 65 536 entries, 256 per sub-region part (fr_api.hip), while one 16-MiB launch of
+    """A launch whose commits log more pairs than a part of the log holds: with chunk_bytes 16 MiB the log
+    has its minimum of 256 entries in each of its 512 parts (fr_api.hip), while one 16-MiB launch of
     34-B records over 300 000 codes logs ~450 000 pairs, ~900 per part.  The pairs past a part's end insert
     straight into the table (commit_buffers' put) during the tally, the rest through the aggregation's
     plain-store inserts afterwards -- mixed on the same codes -- and the tally must equal the oracle's."""
@@ -249,6 +250,46 @@ def test_heavy_chunk_switch(lib):
                 assert d["chunk_tiles"] == 5 and d["heavy_launches"] == 0, (d, launches)
         c.device_free(p)
         c.device_free(q)
+    finally:
+        c.close()
+
+
+def test_mirror_matches_state_readback(lib):
+    """The pinned mirror that log_reduce_kernel's last workgroup writes (the head of DevState, word by word, and
+    the fold statistics) against a real copy of the device state.  Two device-fed files of several 1 MiB launches
+    each, every commit logged (log_min 0): fr_get_diag right after the second feed answers from the mirror; the
+    second file's end runs its presence scan (the first file's is deferred and would hand back the mirror again),
+    so fr_get_diag after it answers from a device-to-host copy.  The entries that the file's end does not change
+    must agree, the mirrored fold statistic must be there, and the tally must equal the oracle's."""
+    from frender_amd import synth
+    sheet = synth.make_sheet(384, 8, 8)
+    files = [synth.generate_bytes(sheet, r0, 60_000, R=8, seed=6) for r0 in (0, 60_000)]
+    assert all(len(d) > 3 << 20 for d in files)  # several launches per file
+    exp = oracle_tally(files)
+    c = lib.Context(device=0, chunk_bytes=1 << 20, table_slots=1 << 16, tuning={"grid": 6})
+    try:
+        c.reset()
+        recs = []
+        for data in files:
+            c.begin_file(None)
+            p = c.device_alloc(len(data) + 16)
+            try:
+                c.copy_to_device(p, data)
+                c.feed_device(p, len(data))
+                mirror = c.diag()
+                st = c.end_file()
+                copied = c.diag()
+            finally:
+                c.device_free(p)
+            assert st.error == 0 and st.exotic == 0
+            recs.append(int(st.records))
+        same = ("spin_max", "spin_total", "keys", "exotic", "chunk_tiles", "heavy_launches")
+        print("mirror", mirror, "copied", copied)
+        assert {k: mirror[k] for k in same} == {k: copied[k] for k in same}
+        assert mirror["keys"] > 0 and mirror["fold_max"] > 0
+        c.finalize()
+        keys, counts, _ = c.unique()
+        assert_same((dict(zip(lib.decode_keys(keys), counts.tolist())), recs), exp)
     finally:
         c.close()
 
