@@ -39,6 +39,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="who inflates the inputs: host (default: the native thread pool) or gpu (BGZF files are "
                         "inflated on the GPU, one member per wave; other files, and every file with -s, stay with "
                         "the host pool; single GPU)")
+    p.add_argument("--single-index", action="store_true",
+                   help="single-indexed library: one barcode per read and no index-2 column in the barcode table "
+                        "(one that exists is ignored).  A read's code is matched by its index 1 alone (the text "
+                        "before a '+', all of it without one); it is demuxable, ambiguous (several rows match) or "
+                        "undetermined.  Not with -rc")
     p.add_argument("files", nargs="+", help="Fastq file(s) or a directory of fastq files")
     p.set_defaults(cmd="scan")
     d = sub.add_parser("demux", help="Demultiplex paired fastq files using a frender scan result file (-r) or the "
@@ -82,6 +87,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "--gz-reader gpu; 1.4-2.0 %% larger; needs --gz-writer gpu)")
     d.add_argument("--gpus", type=int, default=1,
                    help="GPUs (one process each; file pairs are dealt to them, rank 0 writes the outputs)")
+    d.add_argument("--single-index", action="store_true",
+                   help="single-indexed library, as scan --single-index: with -r, a result row with an empty idx2 "
+                        "also answers reads whose code has no '+'; with -b, reads are classified by index 1 alone "
+                        "and the table needs no index-2 column")
     d.add_argument("--stage-times", action="store_true", help="print the demux's seconds per stage (stderr)")
     d.add_argument("files", nargs="+", help="Fastq file, list of fastq files, or directory path")
     d.set_defaults(cmd="demux")
@@ -92,6 +101,9 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     if getattr(args, "cmd", None) == "scan":
+        if args.single_index and args.rc:
+            from .host import SINGLE_RC_REFUSAL
+            parser.error(SINGLE_RC_REFUSAL)
         if args.gz_reader == "gpu" and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
             parser.error("--gz-reader gpu is a single-GPU reader: run it without --gpus (multi-GPU scans inflate on "
                          "the host)")

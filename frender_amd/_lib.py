@@ -95,6 +95,7 @@ _SIGS = {
     "fr_set_timing": (C.c_int, [P, C.c_int]),
     "fr_get_diag": (C.c_int, [P, P, C.c_int]),
     "fr_set_sheet": (C.c_int, [P, C.c_int, P, P, P, P, P, P, C.c_int, P, P, P, C.c_int]),
+    "fr_set_index_mode": (C.c_int, [P, C.c_int]),
     "fr_reset": (C.c_int, [P]),
     "fr_begin_file": (C.c_int, [P, C.c_int64]),
     "fr_begin_file_at": (C.c_int, [P, C.c_int64, C.c_uint64, C.c_int64]),
@@ -129,6 +130,8 @@ _SIGS = {
     "fr_gz_size_hint": (C.c_uint64, [C.c_char_p]),
     "fr_write_scan_csv": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64, P, P, P, P, P, P, P, C.c_char_p, P, P,
                                     C.c_uint64, P, C.c_char_p, P]),
+    "fr_write_scan_csv_mode": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64, P, P, P, P, P, P, P, C.c_char_p, P, P,
+                                         C.c_uint64, P, C.c_char_p, P, C.c_int]),
     "fr_gz_part_bounds": (C.c_int, [C.c_char_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
     "fr_gz_error": (C.c_char_p, [P]),
     "fr_gz_part_open": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int),
@@ -261,6 +264,7 @@ def pack_lower(s: str) -> int:
     return v
 
 
+FR_INDEX_DUAL, FR_INDEX_SINGLE = 0, 1  # fr_set_index_mode
 FR_DMX_MISSING, FR_DMX_BADTYPE, FR_DMX_EXOTIC = -1, -2, -3
 FR_DMX_LEN1, FR_DMX_LEN2, FR_DMX_NOPLUS = -4, -5, -6  # sheet mode: scan's error 1, 2, 3 for the code
 
@@ -735,6 +739,7 @@ class Context:
         if err:
             raise FrenderError(f"fr_create: {err.decode()}")
         self.n_names = 0
+        self.single_index = False  # fr_set_index_mode: the mode of the next set_sheet
         self._sheet_cache: dict = {}
 
     def close(self):
@@ -754,6 +759,11 @@ class Context:
         return rc
 
     # ---- sheet ----------------------------------------------------------------------
+    def set_index_mode(self, single: bool):
+        """FR_INDEX_SINGLE / FR_INDEX_DUAL for the next set_sheet (fr_set_index_mode; reset keeps it)."""
+        self._ck(lib.fr_set_index_mode(self.h, FR_INDEX_SINGLE if single else FR_INDEX_DUAL), "fr_set_index_mode")
+        self.single_index = bool(single)
+
     def set_sheet(self, idx1: list, idx2: list, idx2rc: list, name_id: list, n_names: int):
         last = getattr(self, "_sheet_last", None)
         if last is not None and last[0] == [idx1, idx2, idx2rc, list(name_id), n_names]:

@@ -178,6 +178,8 @@ struct fr_ctx {
     int S = -1;
     int n_names = 0;
     int L1u = -1, L2u = -1;
+    int index_mode = FR_INDEX_DUAL;  // fr_set_index_mode: the mode the next fr_set_sheet uploads in
+    int sheet_single = 0;            // the current sheet was uploaded in FR_INDEX_SINGLE
     u64 *d_i1 = nullptr, *d_i2 = nullptr, *d_i2rc = nullptr;
     int32_t* d_name = nullptr;
     u32 *d_cp1 = nullptr, *d_cp2 = nullptr, *d_cp2rc = nullptr;
@@ -908,6 +910,21 @@ int fr_set_sheet(fr_ctx* ctx, int S, const uint64_t* idx1_packed, const int32_t*
                  const int32_t* name_id, int n_names, const uint32_t* idx1_cp, const uint32_t* idx2_cp,
                  const uint32_t* idx2rc_cp, int cp_stride) {
     if (S < 0 || S > 32767) return fail(ctx, FR_ERR_INVALID, "sheet rows must be in [0, 32767]");
+    // FR_INDEX_SINGLE: every idx2 is the empty string, whatever the caller passed for index 2
+    std::vector<u64> no_packed;
+    std::vector<int32_t> no_len;
+    std::vector<u32> no_cp;
+    const bool single = ctx->index_mode == FR_INDEX_SINGLE;
+    if (single) {
+        no_packed.assign(S + 1, 0);
+        no_len.assign(S + 1, 0);
+        idx2_packed = idx2rc_packed = no_packed.data();
+        idx2_len = no_len.data();
+        if (idx1_cp && cp_stride > 0) {
+            no_cp.assign((u64)(S + 1) * cp_stride, 0);
+            idx2_cp = idx2rc_cp = no_cp.data();
+        }
+    }
     const bool with_cp = idx1_cp && idx2_cp && idx2rc_cp && cp_stride > 0 && S > 0;
     const u64 ncp = with_cp ? (u64)S * cp_stride : 0;
     // blob layout (8-B aligned pieces): i1 i2 i2rc [S] u64 | name [S] i32 | cp1 cp2 cp2rc [S*stride] u32 |
@@ -985,6 +1002,15 @@ int fr_set_sheet(fr_ctx* ctx, int S, const uint64_t* idx1_packed, const int32_t*
     };
     ctx->L1u = common(idx1_len);
     ctx->L2u = common(idx2_len);
+    ctx->sheet_single = single ? 1 : 0;
+    return FR_OK;
+}
+
+int fr_set_index_mode(fr_ctx* ctx, int mode) {
+    if (!ctx) return FR_ERR_INVALID;
+    if (mode != FR_INDEX_DUAL && mode != FR_INDEX_SINGLE)
+        return fail(ctx, FR_ERR_INVALID, "fr_set_index_mode: FR_INDEX_DUAL or FR_INDEX_SINGLE");
+    ctx->index_mode = mode;
     return FR_OK;
 }
 
@@ -1677,6 +1703,8 @@ static int ensure_nbr(fr_ctx* ctx, const SheetArgs& sh, int nsubs, int rc) {
 int fr_classify(fr_ctx* ctx, int num_subs, int rc_mode, int16_t* m1, int16_t* m2, uint8_t* cls, int16_t* row,
                 int16_t* rc_m2, uint8_t* rc_cls, int16_t* rc_row, int64_t* err_unique, int32_t* err_which) {
     if (ctx->S < 0) return fail(ctx, FR_ERR_INVALID, "fr_classify: no sheet");
+    if (ctx->sheet_single && rc_mode)
+        return fail(ctx, FR_ERR_INVALID, "fr_classify: no rc_mode on a single-index sheet (there is no index 2)");
     const u64 n = ctx->U;
     int rc = ensure_class_scratch(ctx, n);
     if (rc) return rc;
@@ -1685,7 +1713,8 @@ int fr_classify(fr_ctx* ctx, int num_subs, int rc_mode, int16_t* m1, int16_t* m2
     // this launch clears whole; d_rcr sits rc_names_cap entries after d_rcf, however many names this sheet has
     u64* blk = ctx->d_errf + (u64)ctx->errf_cur * ctx->errf_words;
     u64* next = ctx->d_errf + (u64)(ctx->errf_cur ^ 1) * ctx->errf_words;
-    SheetArgs sh{ctx->S, ctx->n_names, ctx->L1u, ctx->L2u, ctx->d_i1, ctx->d_i2, ctx->d_i2rc, ctx->d_name};
+    SheetArgs sh{ctx->S, ctx->n_names, ctx->L1u, ctx->L2u, ctx->d_i1, ctx->d_i2, ctx->d_i2rc, ctx->d_name,
+                 ctx->sheet_single};
     if ((rc = ensure_nbr(ctx, sh, num_subs, rc_mode ? 1 : 0))) return rc;
     ClassOut o{ctx->d_m1, ctx->d_m2, ctx->d_cls, ctx->d_row, ctx->d_rm2, ctx->d_rcls, ctx->d_rrow,
                blk + 1, blk + 1 + ctx->rc_names_cap, blk, ctx->d_errw};
@@ -1753,6 +1782,8 @@ int fr_classify_cp(fr_ctx* ctx, int n, const uint32_t* q1, const int32_t* q1len,
                    int32_t* err_which) {
     if (int src = settle_finalize(ctx)) return src;
     if (n <= 0) return FR_OK;
+    if (ctx->sheet_single && rc_mode)
+        return fail(ctx, FR_ERR_INVALID, "fr_classify_cp: no rc_mode on a single-index sheet (there is no index 2)");
     if (ctx->S > 0 && (!ctx->d_cp1 || cp_stride != ctx->cp_stride))
         return fail(ctx, FR_ERR_INVALID, "fr_classify_cp: sheet code points missing or stride mismatch");
     u32 *dq1, *dq2;
@@ -1903,7 +1934,8 @@ namespace fr {
 int borrow_sheet(fr_ctx* ctx, int nsubs, int* device, SheetArgs* sh, NbrMap* nm) {
     if (ctx->S < 0) return fail(ctx, FR_ERR_INVALID, "fr_dmx_set_sheet: no sheet");
     CK(hipSetDevice(ctx->device));
-    *sh = SheetArgs{ctx->S, ctx->n_names, ctx->L1u, ctx->L2u, ctx->d_i1, ctx->d_i2, ctx->d_i2rc, ctx->d_name};
+    *sh = SheetArgs{ctx->S, ctx->n_names, ctx->L1u, ctx->L2u, ctx->d_i1, ctx->d_i2, ctx->d_i2rc, ctx->d_name,
+                    ctx->sheet_single};
     if (int rc = ensure_nbr(ctx, *sh, nsubs, 0)) return rc;
     CK(hipStreamSynchronize(ctx->stream));  // the sheet upload and the map build: the demux reads them on its own stream
     *nm = ctx->nbr;

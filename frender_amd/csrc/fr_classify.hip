@@ -243,8 +243,9 @@ __device__ __forceinline__ PairClass class_pair_nbr(const NbrMap& nm, int a1, in
 // ------------------------------------------------------------------------------------
 // A fast key (symbols A1 C2 G3 T4 N5 '+'6, folded they equal the sheet's a1..n5) split at '+' like
 // idx1, idx2 = code.split("+")[0:2] (frender.py:306), both halves packed 3 bits per letter like the sheet:
-// false without a '+'.
-__device__ __forceinline__ bool split_fast_key(u64 key, int& n1, int& n2, u64& q1, u64& q2) {
+// false without a '+'.  single (a single-index sheet, uniform over the launch): the code is its idx1 alone,
+// code.split("+")[0] -- every symbol without a '+' -- with n2 = 0, q2 = 0 whatever follows; always true.
+__device__ __forceinline__ bool split_fast_key(u64 key, bool single, int& n1, int& n2, u64& q1, u64& q2) {
     // SWAR over the 21 3-bit groups: len = symbols before the first empty group; the '+'
     // groups (== 6) among them give p1, p2 (no per-symbol loop)
     constexpr u64 G0 = 0x1249249249249249ull & ((1ull << 63) - 1ull);  // bit 0 of each group
@@ -265,12 +266,21 @@ __device__ __forceinline__ bool split_fast_key(u64 key, int& n1, int& n2, u64& q
         q1 = n1 ? (key & ((1ull << (3 * n1)) - 1ull)) : 0ull;
         q2 = n2 ? ((key >> (3 * (p1 + 1))) & ((1ull << (3 * n2)) - 1ull)) : 0ull;
     }
-    return plus;
+    if (single) {
+        if (!plus) {
+            n1 = len;
+            q1 = key;
+        }
+        n2 = 0;
+        q2 = 0;
+    }
+    return plus || single;
 }
 
 // The same split of a wide key (fr_internal.h: more than 21 symbols): base-5 letters, the '+' position in
-// bits 57-61 (WIDE_NOPLUS without one).
-__device__ __forceinline__ bool split_wide_key(u64 key, int& n1, int& n2, u64& q1, u64& q2) {
+// bits 57-61 (WIDE_NOPLUS without one).  Either part of a wide key has at most 21 letters (wide_encode), so
+// q1 always fits the packed form, with or without a '+'.
+__device__ __forceinline__ bool split_wide_key(u64 key, bool single, int& n1, int& n2, u64& q1, u64& q2) {
     const u64 V = key & ((1ull << 57) - 1ull);
     const int pp = (int)((key >> 57) & 31u);
     int nl = 0;
@@ -290,10 +300,15 @@ __device__ __forceinline__ bool split_wide_key(u64 key, int& n1, int& n2, u64& q
         if (i < n1) q1 |= sy << (3 * i);
         else q2 |= sy << (3 * (i - n1));
     }
-    return plus;
+    if (single) {
+        n2 = 0;
+        q2 = 0;
+    }
+    return plus || single;
 }
 
-// the length asserts (frender.py:227-229), idx1 list first: 1 idx1, 2 idx2, 0 none
+// the length asserts (frender.py:227-229), idx1 list first: 1 idx1, 2 idx2, 0 none.  A single-index sheet's idx2
+// entries are all empty (L2u = 0) and its codes split with n2 = 0: idx1's length alone decides.
 __device__ __forceinline__ int length_error(const SheetArgs& sh, int n1, int n2) {
     if (sh.S > 0 && (sh.L1u == -2 || sh.L1u != n1)) return 1;
     if (sh.S > 0 && (sh.L2u == -2 || sh.L2u != n2)) return 2;
@@ -333,7 +348,9 @@ __global__ __launch_bounds__(CLS_WG) void classify_kernel(const u64* keys, const
         const u64 key = keys[u];
         int n1 = 0, n2 = 0;
         u64 q1 = 0, q2 = 0;
-        const bool plus = (key & WIDE_BIT) ? split_wide_key(key, n1, n2, q1, q2) : split_fast_key(key, n1, n2, q1, q2);
+        const bool single = sh.single != 0;
+        const bool plus = (key & WIDE_BIT) ? split_wide_key(key, single, n1, n2, q1, q2)
+                                           : split_fast_key(key, single, n1, n2, q1, q2);
         const int err = plus ? length_error(sh, n1, n2) : 3;
         PairClass c = {-1, -1, CLS_UNDET, -1, -1, CLS_UNDET, -1};
         if (!err) {
@@ -422,7 +439,7 @@ __global__ __launch_bounds__(CLS_WG) void dmx_class_kernel(const u64* __restrict
         int n1 = 0, n2 = 0;
         u64 q1 = 0, q2 = 0;
         int32_t d;
-        if (!split_fast_key(rec_key[u], n1, n2, q1, q2)) {
+        if (!split_fast_key(rec_key[u], sh.single != 0, n1, n2, q1, q2)) {
             d = FR_DMX_NOPLUS;
         } else if (const int err = length_error(sh, n1, n2)) {
             d = err == 1 ? FR_DMX_LEN1 : FR_DMX_LEN2;

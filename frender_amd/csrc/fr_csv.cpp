@@ -92,11 +92,14 @@ struct Out {
 
 }  // namespace
 
-extern "C" int fr_write_scan_csv(const char* path, const char* header, uint64_t n_rows, const uint64_t* keys,
-                                 const uint64_t* counts, const int16_t* m1, const int16_t* m2, const uint8_t* cls,
-                                 const int16_t* row, const uint8_t* demux_ok, const char* dict,
-                                 const uint64_t* dict_off, const uint32_t* dict_n, uint64_t n_exotic,
-                                 const uint64_t* exo_rows, const char* exo_text, const uint64_t* exo_off) {
+extern "C" int fr_write_scan_csv_mode(const char* path, const char* header, uint64_t n_rows, const uint64_t* keys,
+                                      const uint64_t* counts, const int16_t* m1, const int16_t* m2,
+                                      const uint8_t* cls, const int16_t* row, const uint8_t* demux_ok,
+                                      const char* dict, const uint64_t* dict_off, const uint32_t* dict_n,
+                                      uint64_t n_exotic, const uint64_t* exo_rows, const char* exo_text,
+                                      const uint64_t* exo_off, int index_mode) {
+    if (index_mode != FR_INDEX_DUAL && index_mode != FR_INDEX_SINGLE) return FR_ERR_INVALID;
+    const bool single = index_mode == FR_INDEX_SINGLE;
     if (!path || !header || (n_rows && (!keys || !counts || !m1 || !m2 || !cls || !row)) || !dict || !dict_off ||
         !dict_n || (n_exotic && (!exo_rows || !exo_text || !exo_off)))
         return FR_ERR_INVALID;
@@ -105,6 +108,7 @@ extern "C" int fr_write_scan_csv(const char* path, const char* header, uint64_t 
     const uint64_t b2 = n1, bs = n1 + n2, bc = n1 + n2 + ns;
     // every code must split on '+' (the reference's code.split("+")[1], frender.py:486): refuse
     // before writing anything, and the caller's own writer raises the reference's IndexError
+    // (single-index scans: a code without '+' is its idx1, with an empty idx2)
     char code[64];
     uint64_t e = 0;
     for (uint64_t j = 0; j < n_rows; ++j) {
@@ -113,7 +117,7 @@ extern "C" int fr_write_scan_csv(const char* path, const char* header, uint64_t 
             continue;
         }
         const int len = decode_key(keys[j], code);
-        if (!memchr(code, '+', (size_t)len)) return FR_ERR_INVALID;
+        if (!single && !memchr(code, '+', (size_t)len)) return FR_ERR_INVALID;
         if ((m1[j] >= 0 && (uint64_t)m1[j] >= n1) || (m2[j] >= 0 && (uint64_t)m2[j] >= n2) ||
             (row[j] >= 0 && (uint64_t)row[j] >= ns) || cls[j] >= nc)
             return FR_ERR_INVALID;
@@ -132,10 +136,15 @@ extern "C" int fr_write_scan_csv(const char* path, const char* header, uint64_t 
         } else {  // parts[0], parts[1] of code.split("+")
             const int len = decode_key(keys[j], code);
             const char* p = (const char*)memchr(code, '+', (size_t)len);
-            const char* q = (const char*)memchr(p + 1, '+', (size_t)(code + len - (p + 1)));
-            o.put(code, (size_t)(p - code));
-            o.ch(',');
-            o.put(p + 1, (size_t)((q ? q : code + len) - (p + 1)));
+            if (!p) {  // single-index only (checked above)
+                o.put(code, (size_t)len);
+                o.ch(',');
+            } else {
+                const char* q = (const char*)memchr(p + 1, '+', (size_t)(code + len - (p + 1)));
+                o.put(code, (size_t)(p - code));
+                o.ch(',');
+                o.put(p + 1, (size_t)((q ? q : code + len) - (p + 1)));
+            }
         }
         o.ch(',');
         if (m1[j] >= 0) entry((uint64_t)m1[j]);
@@ -153,4 +162,13 @@ extern "C" int fr_write_scan_csv(const char* path, const char* header, uint64_t 
     o.flush();
     const bool ok = o.ok && fclose(f) == 0;
     return ok ? FR_OK : FR_ERR_IO;
+}
+
+extern "C" int fr_write_scan_csv(const char* path, const char* header, uint64_t n_rows, const uint64_t* keys,
+                                 const uint64_t* counts, const int16_t* m1, const int16_t* m2, const uint8_t* cls,
+                                 const int16_t* row, const uint8_t* demux_ok, const char* dict,
+                                 const uint64_t* dict_off, const uint32_t* dict_n, uint64_t n_exotic,
+                                 const uint64_t* exo_rows, const char* exo_text, const uint64_t* exo_off) {
+    return fr_write_scan_csv_mode(path, header, n_rows, keys, counts, m1, m2, cls, row, demux_ok, dict, dict_off, dict_n,
+                                  n_exotic, exo_rows, exo_text, exo_off, FR_INDEX_DUAL);
 }

@@ -245,6 +245,7 @@ struct SheetArgs {
     const u64* i2;
     const u64* i2rc;
     const int32_t* name;
+    int single;          // FR_INDEX_SINGLE sheet (fr_set_index_mode): a code is its idx1 alone, L2u is 0
 };
 
 struct ClassOut {
@@ -258,7 +259,7 @@ struct ClassOut {
     u64* rc_f;           // per name
     u64* rc_r;
     u64* err_first;      // ~(min unique index with an error), 0 none (zero-initialised with the rc sums)
-    int32_t* err_which;  // per unique (optional): 1 idx1 len, 2 idx2 len, 3 no '+'
+    int32_t* err_which;  // per unique (optional): 1 idx1 len, 2 idx2 len, 3 no '+' (never on a single-index sheet)
 };
 
 enum { CLS_UNDET = 0, CLS_HOP = 1, CLS_DEMUX = 2, CLS_AMBIG = 3 };

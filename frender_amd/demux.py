@@ -28,15 +28,17 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import demux_mode, get_indexes, gz_format, parse_files
+from .host import demux_mode, get_indexes, gz_format, parse_files, single_index
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
 # the column order `scan` itself writes (frender.py:482-501, report_analysis)
 SCAN_HEADER = ["idx1", "idx2", "matched_idx1", "matched_idx2", "read_type", "sample_name", "reads"]
 
 
-def parse_results_file(result_file, strict: bool = False) -> dict:
-    """frender.py:645-664: code -> (read_type, sample_id).
+def parse_results_file(result_file, strict: bool = False, single: bool = False) -> dict:
+    """frender.py:645-664: code -> (read_type, sample_id).  single (`demux -r --single-index`): a row whose
+    idx2 is empty answers idx1 as well as idx1 + "+" (a single-index scan gives the two the same class);
+    every other row is keyed as ever.
 
     The reference asserts the README's column order, which its own `scan` does not write, so its
     demux rejects its own scan CSV.  Documented deviation, on by default so that
@@ -59,7 +61,14 @@ def parse_results_file(result_file, strict: bool = False) -> dict:
         enabled = gc.isenabled()
         gc.disable()
         try:
-            return {line[0] + "+" + line[1]: (line[ti], line[si]) for line in rd}
+            if not single:
+                return {line[0] + "+" + line[1]: (line[ti], line[si]) for line in rd}
+            out = {}
+            for line in rd:
+                out[line[0] + "+" + line[1]] = (line[ti], line[si])
+                if line[1] == "":
+                    out[line[0]] = (line[ti], line[si])
+            return out
         finally:
             if enabled:
                 gc.enable()
@@ -386,8 +395,11 @@ class SheetMode:
     distinct string once for the whole run) and the exceptions scan raises."""
     _ERR = {_lib.FR_DMX_LEN1: 1, _lib.FR_DMX_LEN2: 2, _lib.FR_DMX_NOPLUS: 3}
 
-    def __init__(self, indexes: dict, num_subs: int, route_of):
+    def __init__(self, indexes: dict, num_subs: int, route_of, single: bool = False):
         self.idx1, self.idx2, self.ids = list(indexes["idx1"]), list(indexes["idx2"]), list(indexes["id"])
+        self.single = bool(single)  # --single-index: a code is its idx1 alone, as scan.process(single=True) takes it
+        if self.single:
+            self.idx2 = [""] * len(self.idx1)
         self.num_subs = int(num_subs)
         self.route_of = route_of
         self.memo = {}       # exotic code -> destination or FR_DMX_LEN1 / _LEN2 / _NOPLUS
@@ -404,6 +416,8 @@ class SheetMode:
             ctx = _lib.Context(device, chunk_bytes=1 << 20, table_slots=1 << 10)
             self.own_ctx = True
         self.ctx = ctx
+        if self.single != getattr(ctx, "single_index", False):
+            ctx.set_index_mode(self.single)
         names, name_id = _sheet_names(self.ids)
         ctx.set_sheet(self.idx1, self.idx2, [reverse_complement(x) for x in self.idx2], name_id, len(names))
         row_dest, class_dest = sheet_destinations(self.ids, self.route_of)
@@ -421,12 +435,12 @@ class SheetMode:
         q1, q2, todo = [], [], []
         for c in new:
             parts = c.split("+")
-            if len(parts) < 2:
+            if len(parts) < 2 and not self.single:
                 self.memo[c] = _lib.FR_DMX_NOPLUS
                 continue
             todo.append(c)
             q1.append(parts[0].lower())
-            q2.append(parts[1].lower())
+            q2.append("" if self.single else parts[1].lower())
         if todo:
             self.classified += len(todo)
             out = self.ctx.classify_cp(q1, q2, self.num_subs, False)
@@ -594,6 +608,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     t_start = time.perf_counter()
     mode = demux_mode(args)
     fmt = gz_format(args)
+    single = single_index(args)
     index_hop = not args.no_index_hop
     ambiguous = not args.no_ambiguous
     undeter = not args.no_undeter
@@ -614,12 +629,12 @@ def frender_demux(args, dev=None, ctx=None) -> None:
         result_file = Path(args.r)
         if not Path.is_file(result_file):
             raise SystemExit(f"File {result_file} not found")
-        results = parse_results_file(result_file, strict=getattr(args, "strict_header", False))
+        results = parse_results_file(result_file, strict=getattr(args, "strict_header", False), single=single)
         ids = sorted({sid for _, sid in results.values()} - {""})
         if (not ids) & samples and lead:
             print(NO_SAMPLES_WARNING)
     else:  # the sheet as scan -b reads it; which ids have reads is known after the last pair only
-        indexes = get_indexes(Path(args.b))
+        indexes = get_indexes(Path(args.b), single)
         ids = sorted(set(indexes["id"]) - {""})
 
     if group is None:
@@ -629,7 +644,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     names, route_of = plan_destinations(ids, samples, undeter, index_hop, ambiguous)
     # destination id -> writer pair (N ranks: its name; rank 0 writes the files at the end)
     writers = [open_files(name, args.d, infix, level, kind) for name in names] if group is None else names
-    sheet = SheetMode(indexes, args.n, route_of) if mode == "b" else None
+    sheet = SheetMode(indexes, args.n, route_of, single) if mode == "b" else None
     lazy = set(range(len(ids))) if sheet is not None and samples else set()  # sample destinations (-b: kept if hit)
     hit = set()
 

@@ -66,8 +66,21 @@ def get_col(match_pattern: str, cols, discard_pattern: str | None = None) -> int
         f"""Couldn't find column matching "{match_pattern}"{' but not "' + discard_pattern + '"' if discard_pattern is not None else ''} in csv header {cols}""")
 
 
-def get_indexes(barcode_file) -> dict:
-    """frender.py:90-116 — {"id": [...], "idx1": [...], "idx2": [...]} in sheet row order."""
+SINGLE_RC_REFUSAL = "--single-index and -rc exclude each other: there is no index 2 to reverse-complement"
+
+
+def single_index(args) -> bool:
+    """--single-index of a scan's or demux's arguments (a namespace without the field, as the reference's,
+    means dual).  With -rc it is refused, before anything is opened."""
+    single = bool(getattr(args, "single_index", False))
+    if single and getattr(args, "rc", False):
+        raise SystemExit(SINGLE_RC_REFUSAL)
+    return single
+
+
+def get_indexes(barcode_file, single: bool = False) -> dict:
+    """frender.py:90-116 — {"id": [...], "idx1": [...], "idx2": [...]} in sheet row order.  single
+    (--single-index): no index-2 column is looked for, one that exists is ignored, every idx2 is ""."""
     skip = handle_illumina_csv(barcode_file)
     with open(barcode_file, "r") as f:
         reader = csv.reader(f)
@@ -77,7 +90,7 @@ def get_indexes(barcode_file) -> dict:
         try:
             id_col = get_col("id|name", header)
             idx1_col = get_col("index", header, "id|2")
-            idx2_col = get_col("index.*2", header)
+            idx2_col = None if single else get_col("index.*2", header)
         except ValueError as e:
             print("Error finding columns in provided barcode file:")
             raise SystemExit(e)
@@ -85,7 +98,7 @@ def get_indexes(barcode_file) -> dict:
         for row in reader:
             out["id"].append(row[id_col])
             out["idx1"].append(row[idx1_col])
-            out["idx2"].append(row[idx2_col])
+            out["idx2"].append("" if single else row[idx2_col])
         return out
 
 

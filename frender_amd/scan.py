@@ -33,7 +33,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import find_barcode_file, get_cores, get_indexes, parse_files, reverse_complement
+from .host import (SINGLE_RC_REFUSAL, find_barcode_file, get_cores, get_indexes, parse_files, reverse_complement,
+                   single_index)
 
 UNDET, HOP, DEMUX, AMBIG = 0, 1, 2, 3
 CLASS_NAMES = _lib.CLASS_NAMES
@@ -283,6 +284,7 @@ class Results:
             self.rc_row = np.full(n, -1, np.int16)
         self.rc_f = None
         self.rc_r = None
+        self.single = False           # classified in single-index mode (process(single=True))
         self.n_total = n              # codes of the whole scan (all key partitions of a multi-GPU scan)
         self.idx1 = self.idx2 = self.ids = None
         self.names = None
@@ -315,13 +317,23 @@ def _lead(table) -> bool:
     return table.group is None or table.group.get_rank() == 0
 
 
-def process(cores, table: UniqueTable, indexes: dict, num_subs: int, rc_mode: bool, ctx=None) -> Results:
+def process(cores, table: UniqueTable, indexes: dict, num_subs: int, rc_mode: bool, ctx=None,
+            single: bool = False) -> Results:
     """frender.py:391-426 on the GPU: classify every unique code (fast keys by packed
     Hamming, exotic codes by the code-point classifier); raise the reference's first error.
     On a key partition (multi-GPU): each rank classifies its partition; the -rc per-name sums are
-    all-reduced and the first error in first-occurrence order over all partitions is raised."""
+    all-reduced and the first error in first-occurrence order over all partitions is raised.
+    single (--single-index, not in the reference): a code is code.split("+")[0] alone, classified as the
+    reference classifies idx1 + "+" against a sheet whose idx2 are all "" (DESIGN.md §4.4); only idx1's
+    length can be in error, and there is no -rc."""
     ctx = ctx or default_context()
     idx1, idx2, ids = list(indexes["idx1"]), list(indexes["idx2"]), list(indexes["id"])
+    if single:
+        if rc_mode:
+            raise SystemExit(SINGLE_RC_REFUSAL)
+        idx2 = [""] * len(idx1)
+    if single != getattr(ctx, "single_index", False):
+        ctx.set_index_mode(single)
     names, name_id = _sheet_names(ids)
     ctx.set_sheet(idx1, idx2, [reverse_complement(x) for x in idx2], name_id, len(names))
     if cores > 1 and _lead(table):
@@ -329,6 +341,7 @@ def process(cores, table: UniqueTable, indexes: dict, num_subs: int, rc_mode: bo
     n = len(table)
     res = Results(n, rc_mode)
     res.idx1, res.idx2, res.ids, res.names = idx1, idx2, ids, names
+    res.single = single
     errs = []  # (merged position, exception)
     fsel = np.nonzero(table.fast_idx >= 0)[0]
     if fsel.size:
@@ -347,12 +360,12 @@ def process(cores, table: UniqueTable, indexes: dict, num_subs: int, rc_mode: bo
         split_ok, q1, q2, js = [], [], [], []
         for j in esel.tolist():
             parts = table.codes[j].split("+")
-            if len(parts) < 2:
+            if len(parts) < 2 and not single:
                 errs.append((j, 3))
                 continue
             js.append(j)
             q1.append(parts[0].lower())
-            q2.append(parts[1].lower())
+            q2.append("" if single else parts[1].lower())
         if js:
             out = ctx.classify_cp(q1, q2, num_subs, rc_mode)
             ja = np.array(js)
@@ -547,15 +560,19 @@ def _csv_fields(*fields) -> str:
     return buf.getvalue()[:-len(",x\r\n")]
 
 
-def _write_csv_native(path, header, keys, exo_pos, exo_codes, counts, m1, m2, cls, row, dok, idx1, idx2, ids) -> bool:
-    """fr_write_scan_csv (fr_csv.cpp): the rows formatted from the packed keys and the classification
+def _write_csv_native(path, header, keys, exo_pos, exo_codes, counts, m1, m2, cls, row, dok, idx1, idx2, ids,
+                      single=False) -> bool:
+    """fr_write_scan_csv_mode (fr_csv.cpp): the rows formatted from the packed keys and the classification
     arrays.  False, with nothing written, when some code does not split on '+' (the caller's row
-    loop then raises the reference's IndexError where the reference does)."""
+    loop then raises the reference's IndexError where the reference does); single: such a code is a row
+    with an empty idx2."""
     texts = []
     for c in exo_codes:
         parts = c.split("+")
         if len(parts) < 2:
-            return False
+            if not single:
+                return False
+            parts.append("")
         texts.append(_csv_fields(parts[0], parts[1]).encode("utf-8", "surrogateescape"))
     ents = [_csv_fields(x).encode("utf-8", "surrogateescape") for x in (*idx1, *idx2, *ids, *CLASS_NAMES)]
     dict_off = np.concatenate([[0], np.cumsum([len(e) for e in ents])]).astype(np.uint64)
@@ -568,13 +585,14 @@ def _write_csv_native(path, header, keys, exo_pos, exo_codes, counts, m1, m2, cl
            np.ascontiguousarray(m1, np.int16), np.ascontiguousarray(m2, np.int16), np.ascontiguousarray(cls, np.uint8),
            np.ascontiguousarray(row, np.int16)]
     d = None if dok is None else np.ascontiguousarray(dok, np.uint8)
-    rc = _lib.lib.fr_write_scan_csv(os.fsencode(path), header.encode(), len(arr[0]), *[_lib._ptr(a) for a in arr],
-                                    _lib._ptr(d), b"".join(ents), _lib._ptr(dict_off), _lib._ptr(dict_n),
-                                    len(exo_rows), _lib._ptr(exo_rows), exo_text, _lib._ptr(exo_off))
+    rc = _lib.lib.fr_write_scan_csv_mode(os.fsencode(path), header.encode(), len(arr[0]), *[_lib._ptr(a) for a in arr],
+                                         _lib._ptr(d), b"".join(ents), _lib._ptr(dict_off), _lib._ptr(dict_n),
+                                         len(exo_rows), _lib._ptr(exo_rows), exo_text, _lib._ptr(exo_off),
+                                         _lib.FR_INDEX_SINGLE if single else _lib.FR_INDEX_DUAL)
     if rc == _lib.FR_ERR_INVALID:
         return False
     if rc != 0:
-        raise OSError(f"fr_write_scan_csv failed ({rc}) writing {path}")
+        raise OSError(f"fr_write_scan_csv_mode failed ({rc}) writing {path}")
     return True
 
 
@@ -582,7 +600,8 @@ def report_analysis(table: UniqueTable, results: Results, demux_ok, out_csv_name
     """frender.py:482-501: the scan CSV (excel dialect, columns in the code's order).  On a key
     partition (multi-GPU) rank 0 gathers every partition's rows and writes the file.  The rows are
     formatted natively from the packed keys (fr_write_scan_csv); the row loop below is kept for the
-    codes that do not split on '+', where it raises the reference's IndexError at the same row."""
+    codes that do not split on '+', where it raises the reference's IndexError at the same row (a
+    single-index scan's code without '+' is a row with an empty idx2, in both writers)."""
     if table.group is not None:
         got = _gather_partitions(table, results, demux_ok)
         if got is None:
@@ -602,7 +621,7 @@ def report_analysis(table: UniqueTable, results: Results, demux_ok, out_csv_name
     if dok is not None:
         header.append("demux_ok")
     if _write_csv_native(out_csv_name, _csv_fields(*header) + "\r\n", keys, exo_pos, exo_codes, counts, m1, m2, cls,
-                         row, dok, idx1, idx2, ids):
+                         row, dok, idx1, idx2, ids, single=results.single):
         return
     codes = Codes(keys, exo_pos, exo_codes)
     m1, m2, cls, row, counts = m1.tolist(), m2.tolist(), cls.tolist(), row.tolist(), counts.tolist()
@@ -611,6 +630,8 @@ def report_analysis(table: UniqueTable, results: Results, demux_ok, out_csv_name
     def rows():
         for j, code in enumerate(codes):
             parts = code.split("+")
+            if results.single and len(parts) < 2:
+                parts.append("")
             r = [parts[0], parts[1], idx1[m1[j]] if m1[j] >= 0 else "", idx2[m2[j]] if m2[j] >= 0 else "",
                  CLASS_NAMES[cls[j]], ids[row[j]] if row[j] >= 0 else "", counts[j]]
             if dok is not None:
@@ -643,6 +664,7 @@ def frender_scan(args, ctx=None) -> dict:
     """frender.py:567-642 with the hot path on the GPU."""
     num_subs = args.n
     rc_mode = args.rc
+    single = single_index(args)  # with -rc: refused here, before any file is opened
     cores = get_cores(args.c)
     sample = args.s
     user_infix = args.o if args.o else ""
@@ -654,7 +676,7 @@ def frender_scan(args, ctx=None) -> dict:
         barcode_file = find_barcode_file(Path(args.files[0]))
     else:
         barcode_file = Path(args.b)
-    indexes = get_indexes(barcode_file)
+    indexes = get_indexes(barcode_file, single)
     out_csv_name, spec = output_name(num_subs, user_infix, args.files)
     files = parse_files(spec, just_r1=True)
     ctx = ctx or default_context()
@@ -662,7 +684,7 @@ def frender_scan(args, ctx=None) -> dict:
     lead = _lead(table)  # multi-GPU: every rank holds a key partition; rank 0 prints and writes
     if lead:
         print("Scanning complete! Analyzing barcodes...")
-    results = process(cores, table, indexes, num_subs, rc_mode, ctx=ctx)
+    results = process(cores, table, indexes, num_subs, rc_mode, ctx=ctx, single=single)
     if rc_mode:
         rc_calls = call_rc_mode_per_id(results, indexes["id"])
         if lead:

@@ -221,10 +221,12 @@ def tally_barcodes(cores, files, sample=None, ctx=None) -> BarcodeCounter:
         _lib.gz_trim()
 
 
-def process(cores, barcode_counter, indexes, num_subs, rc_mode, ctx=None) -> ResultsMapping:
-    """frender.py:391-426 on the GPU (frender_amd.scan.process), the reference's shape."""
+def process(cores, barcode_counter, indexes, num_subs, rc_mode, ctx=None, single=False) -> ResultsMapping:
+    """frender.py:391-426 on the GPU (frender_amd.scan.process), the reference's shape.  single: a
+    single-indexed library (indexes from get_indexes(sheet, single=True); not in the reference)."""
     table, index = _table_of(barcode_counter)
-    return ResultsMapping(table, _scan.process(cores, table, indexes, num_subs, rc_mode, ctx=ctx), index)
+    return ResultsMapping(table, _scan.process(cores, table, indexes, num_subs, rc_mode, ctx=ctx, single=single),
+                          index)
 
 
 def call_rc_mode_per_id(results_list, ids) -> dict:

@@ -130,6 +130,18 @@ int fr_set_sheet(fr_ctx* ctx, int S,
                  const uint64_t* idx2rc_packed, const int32_t* name_id, int n_names,
                  const uint32_t* idx1_cp, const uint32_t* idx2_cp, const uint32_t* idx2rc_cp,
                  int cp_stride);
+/* Index mode of the context (FR_INDEX_DUAL when it is created; fr_reset keeps it).  It takes effect at the next
+ * fr_set_sheet.  FR_INDEX_SINGLE, for single-indexed libraries (one barcode per read, no index 2 in the
+ * sheet): fr_set_sheet reads no idx2 argument (they may be NULL) and uploads every idx2 as the empty
+ * string, and on such a sheet fr_classify, fr_dmx_set_sheet's records and fr_classify_cp's callers take a code
+ * as its idx1 alone: code.split("+")[0], every character when it has no '+', against the empty idx2.  So a
+ * code is classified as the reference classifies idx1 + "+" against a sheet whose idx2 are all "": with M the
+ * rows whose idx1 is within num_subs mismatches, undetermined (|M| = 0), demuxable (1) or ambiguous (>= 2,
+ * m1 = the first of them); never an index hop, m2 = 0 (the empty entry) whenever m1 >= 0.  Only idx1's length
+ * is asserted (error 1); errors 2 and 3 and FR_DMX_LEN2 / FR_DMX_NOPLUS do not occur.  rc_mode is refused. */
+#define FR_INDEX_DUAL 0
+#define FR_INDEX_SINGLE 1
+int fr_set_index_mode(fr_ctx* ctx, int mode);
 
 /* ---- tally: replaces tally_barcodes (frender.py:183-207) / scan_file (:154-181) ----
  * Files are fed in parse_files order (:604); fr_reset starts a new scan. */
@@ -222,6 +234,15 @@ int fr_write_scan_csv(const char* path, const char* header, uint64_t n_rows, con
                       const int16_t* row, const uint8_t* demux_ok, const char* dict, const uint64_t* dict_off,
                       const uint32_t* dict_n, uint64_t n_exotic, const uint64_t* exo_rows, const char* exo_text,
                       const uint64_t* exo_off);
+/* The same with the scan's index mode.  FR_INDEX_DUAL: fr_write_scan_csv exactly.  FR_INDEX_SINGLE: a keyed
+ * code without '+' is a row too, its idx1 field the whole code and its idx2 field empty (a code with a '+'
+ * splits as above, so ACGT, ACGT+ and ACGT+TTTT are three rows). */
+int fr_write_scan_csv_mode(const char* path, const char* header, uint64_t n_rows, const uint64_t* keys,
+                           const uint64_t* counts, const int16_t* m1, const int16_t* m2, const uint8_t* cls,
+                           const int16_t* row, const uint8_t* demux_ok, const char* dict,
+                           const uint64_t* dict_off, const uint32_t* dict_n, uint64_t n_exotic,
+                           const uint64_t* exo_rows, const char* exo_text, const uint64_t* exo_off,
+                           int index_mode);
 const char* fr_gz_error(const fr_gz* g);
 void fr_gz_close(fr_gz* g);
 /* Decode buffers outlive their pool: a process-wide cache keeps up to 4 GiB of them for the next scan
