@@ -13,6 +13,7 @@ the same, so one pass over the inputs writes what scan + demux -r write in two.
 """
 from __future__ import annotations
 
+import contextlib
 import csv
 import gc
 import gzip
@@ -28,7 +29,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import demux_mode, get_indexes, gz_format, parse_files, single_index
+from .host import demux_mode, get_indexes, gz_format, input_spec, parse_files, single_index
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
 # the column order `scan` itself writes (frender.py:482-501, report_analysis)
@@ -96,6 +97,15 @@ _LD = _load_libdeflate()
 _LD_TLS = threading.local()
 
 
+def _fetched_window(dmx, mate, n_dest, routed):
+    """Every writer class has window(dmx, mate, n_dest, routed), the one Demux call of its family for a routed
+    window -> (arr, sizes, extras), and write(arr, start, end, *extra), which appends arr[start:end] to the file:
+    destination k's range is sizes[k] long, after those before it, and extras[k] are its further arguments
+    (extras is empty when there are none).  This is the window of the writers that compress on the host: the
+    routed bytes as they are."""
+    return dmx.fetch(mate, int(routed.sum())), routed, ()
+
+
 class _GzMembers:
     """A .fq.gz writer that compresses every write into its own gzip member with libdeflate (ctypes
     releases the GIL, so the writers of one window compress in parallel threads).  A multi-member
@@ -109,6 +119,8 @@ class _GzMembers:
         self.level = level
         self.wrote = False
 
+    window = staticmethod(_fetched_window)
+
     def _compressor(self):
         c = getattr(_LD_TLS, "c", None)
         if c is None:
@@ -120,7 +132,7 @@ class _GzMembers:
                 raise MemoryError("libdeflate_alloc_compressor")
         return h
 
-    def write_from(self, arr: np.ndarray, start: int, end: int) -> None:
+    def write(self, arr: np.ndarray, start: int, end: int) -> None:
         import ctypes
 
         n = end - start
@@ -152,7 +164,12 @@ class _GzDevice:
         self.level = level
         self.wrote = False
 
-    def write_member(self, arr: np.ndarray, start: int, end: int, crc: int, isize: int) -> None:
+    @staticmethod
+    def window(dmx, mate, n_dest, routed):
+        sizes, crc, arr = dmx.deflate(mate, n_dest)
+        return arr, sizes, list(zip(crc, routed))  # a member's trailer: the CRC-32 and length of its text
+
+    def write(self, arr: np.ndarray, start: int, end: int, crc: int, isize: int) -> None:
         if end <= start:
             return
         head, tail = _lib.gzip_frame(int(crc), int(isize))
@@ -177,7 +194,12 @@ class _BgzfDevice:
         self.f = open(path, "wb")
         self.level = level
 
-    def write_members(self, arr: np.ndarray, start: int, end: int) -> None:
+    @staticmethod
+    def window(dmx, mate, n_dest, routed):
+        sizes, arr = dmx.deflate_bgzf(mate, n_dest)
+        return arr, sizes, ()
+
+    def write(self, arr: np.ndarray, start: int, end: int) -> None:
         if end > start:
             self.f.write(memoryview(arr)[start:end])
 
@@ -193,12 +215,13 @@ class _BgzfPart(_BgzfDevice):
 
 
 class _GzFile:
-    """gzip.open writer with the same write_from interface (the image has no libdeflate)."""
+    """gzip.open writer (the image has no libdeflate)."""
+    window = staticmethod(_fetched_window)
 
     def __init__(self, path: str, level: int):
         self.f = gzip.open(path, "wb", compresslevel=level)
 
-    def write_from(self, arr: np.ndarray, start: int, end: int) -> None:
+    def write(self, arr: np.ndarray, start: int, end: int) -> None:
         if end > start:
             self.f.write(memoryview(arr)[start:end])
 
@@ -342,6 +365,11 @@ def _tail(parts, start: int) -> list:
     return []
 
 
+def _code_at(bufs, start: int) -> str:
+    """The code of the R2 record whose header line starts at byte `start` of R2's window (frender.py:778)."""
+    return _line_at(bufs[1], start).split(b":")[-1].decode("utf-8")
+
+
 STAGE_TIMES = {}  # seconds per stage of _demux_pair's windows (demux --stage-times prints them)
 
 
@@ -393,13 +421,11 @@ class SheetMode:
     object is the host's part: the sheet context of this process's GPU, the codes outside the fast
     alphabet (case-folded, classified over code points as scan.process classifies exotic codes, each
     distinct string once for the whole run) and the exceptions scan raises."""
-    _ERR = {_lib.FR_DMX_LEN1: 1, _lib.FR_DMX_LEN2: 2, _lib.FR_DMX_NOPLUS: 3}
+    _ERR = {_lib.FR_DMX_LEN1: 1, _lib.FR_DMX_LEN2: 2, _lib.FR_DMX_NOPLUS: 3}  # destination value <-> scan's error
 
     def __init__(self, indexes: dict, num_subs: int, route_of, single: bool = False):
-        self.idx1, self.idx2, self.ids = list(indexes["idx1"]), list(indexes["idx2"]), list(indexes["id"])
+        self.idx1, self.idx2, self.ids = indexes["idx1"], indexes["idx2"], indexes["id"]  # as uploaded, once bound
         self.single = bool(single)  # --single-index: a code is its idx1 alone, as scan.process(single=True) takes it
-        if self.single:
-            self.idx2 = [""] * len(self.idx1)
         self.num_subs = int(num_subs)
         self.route_of = route_of
         self.memo = {}       # exotic code -> destination or FR_DMX_LEN1 / _LEN2 / _NOPLUS
@@ -410,16 +436,12 @@ class SheetMode:
     def bind(self, dmx, device: int, ctx=None):
         """Upload the sheet to a context of `device` (a small one of our own unless the caller has one: it
         never tallies) and put dmx into sheet mode."""
-        from .host import reverse_complement
-        from .scan import _sheet_names
+        from .scan import upload_sheet
         if ctx is None:
             ctx = _lib.Context(device, chunk_bytes=1 << 20, table_slots=1 << 10)
             self.own_ctx = True
         self.ctx = ctx
-        if self.single != getattr(ctx, "single_index", False):
-            ctx.set_index_mode(self.single)
-        names, name_id = _sheet_names(self.ids)
-        ctx.set_sheet(self.idx1, self.idx2, [reverse_complement(x) for x in self.idx2], name_id, len(names))
+        self.idx1, self.idx2, self.ids, _, _ = upload_sheet(ctx, (self.idx1, self.idx2, self.ids), self.single)
         row_dest, class_dest = sheet_destinations(self.ids, self.route_of)
         dmx.set_sheet(ctx, self.num_subs, row_dest, class_dest)
 
@@ -429,25 +451,21 @@ class SheetMode:
         self.ctx = None
 
     def resolve(self, codes) -> list:
-        """Destinations of exotic codes (scan.process's exotic branch: split at '+', case-fold,
-        classify_cp, the same error rules)."""
+        """Destinations of exotic codes (scan.process's exotic branch: scan.split_exotic, classify_cp, the
+        same error rules)."""
+        from .scan import split_exotic
         new = [c for c in dict.fromkeys(codes) if c not in self.memo]
-        q1, q2, todo = [], [], []
-        for c in new:
-            parts = c.split("+")
-            if len(parts) < 2 and not self.single:
-                self.memo[c] = _lib.FR_DMX_NOPLUS
-                continue
-            todo.append(c)
-            q1.append(parts[0].lower())
-            q2.append("" if self.single else parts[1].lower())
-        if todo:
-            self.classified += len(todo)
+        kept, q1, q2, bare = split_exotic(new, self.single)
+        for k in bare:
+            self.memo[new[k]] = _lib.FR_DMX_NOPLUS
+        if kept:
+            self.classified += len(kept)
             out = self.ctx.classify_cp(q1, q2, self.num_subs, False)
-            for k, c in enumerate(todo):
+            val_of = {which: val for val, which in self._ERR.items()}
+            for k, c in enumerate(new[j] for j in kept):
                 err = int(out["err"][k])
                 if err:
-                    self.memo[c] = {1: _lib.FR_DMX_LEN1, 2: _lib.FR_DMX_LEN2}.get(err, _lib.FR_DMX_NOPLUS)
+                    self.memo[c] = val_of.get(err, _lib.FR_DMX_NOPLUS)
                     continue
                 name = _lib.CLASS_NAMES[int(out["cls"][k])]
                 sid = self.ids[int(out["row"][k])] if name == "demuxable" else ""
@@ -472,8 +490,7 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
     bufs = [[], []]  # each mate's window as a list of decoded blocks (never joined on the host)
     eof = [False, False]
     pending = []  # the previous window's gzip jobs: overlap with this window's inflate and GPU work
-    st = STAGE_TIMES
-    clock = time.perf_counter
+    st, clock = STAGE_TIMES, time.perf_counter
     try:
         while True:
             t0 = clock()
@@ -501,20 +518,15 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
             ex = dmx.exotic(n_pairs)
             if ex.size:  # codes outside the fast alphabet: resolve by string
                 starts, _ = dmx.records(1, ex)
-                dest = []
-                if sheet is not None:
-                    dest = sheet.resolve([_line_at(bufs[1], s).split(b":")[-1].decode("utf-8") for s in starts.tolist()])
-                else:
-                    for s in starts.tolist():
-                        code = _line_at(bufs[1], s).split(b":")[-1].decode("utf-8")
-                        row = results.get(code)
-                        dest.append(_lib.FR_DMX_MISSING if row is None else route_of(row))
+                codes = [_code_at(bufs, s) for s in starts.tolist()]
+                dest = sheet.resolve(codes) if sheet is not None else \
+                    [route_of(results[c]) if c in results else _lib.FR_DMX_MISSING for c in codes]
                 dmx.patch(ex, np.array(dest, dtype=np.int32))
             first, val, b1, b2 = dmx.route(len(writers), n_pairs)
             t3 = clock()
             if first >= 0:
                 s, _ = dmx.records(1, [first])
-                code = _line_at(bufs[1], int(s[0])).split(b":")[-1].decode("utf-8")
+                code = _code_at(bufs, int(s[0]))
                 if val == _lib.FR_DMX_MISSING:
                     raise SystemExit(f"Couldn't find barcode {code} in supplied frender result file!")
                 err = sheet.error(code, val) if sheet is not None else None
@@ -523,48 +535,18 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 raise SystemExit("Unrecognized read type found in supplied frender result file!")
             if hit is not None:
                 hit.update(np.nonzero(b1 + b2)[0].tolist())
-            if isinstance(writers[0]["R1"], _BgzfDevice):  # the GPU makes every destination's BGZF members
-                z1, o1 = dmx.deflate_bgzf(0, len(writers))
-                z2, o2 = dmx.deflate_bgzf(1, len(writers))
-                t4 = clock()
-                for j in pending:
-                    j.result()
-                c1 = np.concatenate([[0], np.cumsum(z1)]).astype(np.int64)
-                c2 = np.concatenate([[0], np.cumsum(z2)]).astype(np.int64)
-                pending = []
-                for k, w in enumerate(writers):
-                    if b1[k]:
-                        pending.append(pool.submit(w["R1"].write_members, o1, int(c1[k]), int(c1[k + 1])))
-                    if b2[k]:
-                        pending.append(pool.submit(w["R2"].write_members, o2, int(c2[k]), int(c2[k + 1])))
-            elif isinstance(writers[0]["R1"], _GzDevice):  # the GPU deflates every destination's bytes
-                z1, k1, o1 = dmx.deflate(0, len(writers))
-                z2, k2, o2 = dmx.deflate(1, len(writers))
-                t4 = clock()
-                for j in pending:
-                    j.result()
-                c1 = np.concatenate([[0], np.cumsum(z1)]).astype(np.int64)
-                c2 = np.concatenate([[0], np.cumsum(z2)]).astype(np.int64)
-                pending = []
-                for k, w in enumerate(writers):
-                    if b1[k]:
-                        pending.append(pool.submit(w["R1"].write_member, o1, int(c1[k]), int(c1[k + 1]), k1[k], b1[k]))
-                    if b2[k]:
-                        pending.append(pool.submit(w["R2"].write_member, o2, int(c2[k]), int(c2[k + 1]), k2[k], b2[k]))
-            else:
-                o1 = dmx.fetch(0, int(b1.sum()))
-                o2 = dmx.fetch(1, int(b2.sum()))
-                t4 = clock()
-                for j in pending:
-                    j.result()
-                c1 = np.concatenate([[0], np.cumsum(b1)]).astype(np.int64)
-                c2 = np.concatenate([[0], np.cumsum(b2)]).astype(np.int64)
-                pending = []
-                for k, w in enumerate(writers):
-                    if b1[k]:
-                        pending.append(pool.submit(w["R1"].write_from, o1, int(c1[k]), int(c1[k + 1])))
-                    if b2[k]:
-                        pending.append(pool.submit(w["R2"].write_from, o2, int(c2[k]), int(c2[k + 1])))
+            # each mate's bytes for the files and their per-destination sizes, as the writers' family makes them
+            wins = [type(writers[0]["R1"]).window(dmx, m, len(writers), b) for m, b in ((0, b1), (1, b2))]
+            t4 = clock()
+            for j in pending:
+                j.result()
+            cums = [np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64) for _, sizes, _ in wins]
+            pending = []
+            for k, w in enumerate(writers):
+                for (arr, _, extras), c, routed, read in zip(wins, cums, (b1, b2), ("R1", "R2")):
+                    if routed[k]:
+                        pending.append(pool.submit(w[read].write, arr, int(c[k]), int(c[k + 1]),
+                                                   *(extras[k] if extras else ())))
             t5 = clock()
             for k, v in (("inflate+join", t1 - t0), ("load+index", t2 - t1), ("route", t3 - t2), ("deflate/fetch", t4 - t3),
                          ("wait writers", t5 - t4)):
@@ -592,10 +574,60 @@ def _drop_unhit(names, lazy, hit, out_dir, infix) -> None:
     `lazy` that `hit` lacks (after their writers are closed)."""
     for k in sorted(lazy - hit):
         for read in ("R1", "R2"):
-            try:
+            with contextlib.suppress(FileNotFoundError):
                 os.unlink(out_path(names[k], out_dir, infix, read))
-            except FileNotFoundError:
-                pass
+
+
+def _close_writers(writers, names, lazy, hit, out_dir, infix) -> None:
+    """Close a destination list's writer pairs in out_dir, then drop the sample pairs nothing was routed to."""
+    for w in writers:
+        for f in w.values():
+            f.close()
+    _drop_unhit(names, lazy, hit, out_dir, infix)
+
+
+@contextlib.contextmanager
+def _session(t_start, paths, kind, n_dest, device, sheet, table, dev=None, ctx=None, finish=None):
+    """What one process demultiplexes with, on one GPU or as a rank of N: (dmx, pool, gz).  gz, the inflate
+    pool over `paths`, comes first: with the GPU compressing, the host's cores inflate (a big single-member
+    file in parallel), and its workers start at once, so the first blocks decode while the device context
+    comes up.  dmx is the caller's `dev` or a Demux of `device`, bound to the sheet (on the caller's `ctx`, if
+    any) or to the results' `table` (keys, vals); pool runs the writers' jobs.  The way out, in one order:
+    inflate pool, writer pool, finish() (the caller's writers), the device (a caller's `dev` stays open),
+    the sheet context.  STAGE_TIMES gets its setup and finish entries (t_start: when the command began)."""
+    st, clock = STAGE_TIMES, time.perf_counter
+    gz = dmx = pool = None
+    try:
+        nt = _inflate_threads(kind)
+        gz = _lib.GzPool(paths, threads=nt, ahead=_lib.inflate_ahead(paths, nt))
+        st["setup: results, writers"] = clock() - t_start
+        dmx = dev or _lib.Demux(device)
+        pool = ThreadPoolExecutor(max_workers=max(2, min(32, n_dest * 2)))
+        if sheet is not None:
+            sheet.bind(dmx, device, ctx)
+        else:
+            dmx.set_table(*table)
+        st["setup"] = clock() - t_start  # results, writers, device table, pool
+        yield dmx, pool, gz
+    finally:
+        t_end = clock()
+        if gz is not None:
+            gz.close()
+        t_gz = clock()
+        if pool is not None:
+            pool.shutdown(wait=True)
+        t_pool = clock()
+        if finish is not None:
+            finish()
+        t_files = clock()
+        if dmx is not None and dev is None:
+            dmx.close()
+        elif dmx is not None and sheet is not None:
+            dmx.set_table(np.zeros(0, np.uint64), np.zeros(0, np.int32))  # end the borrow of the sheet context
+        if sheet is not None:
+            sheet.close()
+        st.update({"finish: inflate pool": t_gz - t_end, "finish: writer pool": t_pool - t_gz,
+                   "finish: files": t_files - t_pool, "finish": clock() - t_end})  # finish: last writes, closes
 
 
 NO_SAMPLES_WARNING = "Warning: no demuxable sample ids found in the supplied frender result file!"
@@ -609,9 +641,6 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     mode = demux_mode(args)
     fmt = gz_format(args)
     single = single_index(args)
-    index_hop = not args.no_index_hop
-    ambiguous = not args.no_ambiguous
-    undeter = not args.no_undeter
     samples = not args.no_samples
     level = getattr(args, "gz_level", None) or 9  # gzip.open's default, as the reference writes
     kind = writer_kind(getattr(args, "gz_writer", None) or "gpu", fmt)
@@ -641,79 +670,36 @@ def frender_demux(args, dev=None, ctx=None) -> None:
         os.mkdir(args.d)
     else:
         _mkdir_everywhere(group, args.d)
-    names, route_of = plan_destinations(ids, samples, undeter, index_hop, ambiguous)
+    names, route_of = plan_destinations(ids, samples, not args.no_undeter, not args.no_index_hop, not args.no_ambiguous)
     # destination id -> writer pair (N ranks: its name; rank 0 writes the files at the end)
     writers = [open_files(name, args.d, infix, level, kind) for name in names] if group is None else names
     sheet = SheetMode(indexes, args.n, route_of, single) if mode == "b" else None
     lazy = set(range(len(ids))) if sheet is not None and samples else set()  # sample destinations (-b: kept if hit)
     hit = set()
 
-    keys = vals = fast = None
+    table = None
     if mode == "r":
         codes = list(results.keys())
         keys, fast = _lib.pack_fast(codes)
-        vals = np.array([route_of(results[c]) for c in codes], dtype=np.int32)
+        table = keys[fast], np.array([route_of(results[c]) for c in codes], dtype=np.int32)[fast]
 
-    if len(args.files) == 1:
-        file = Path(args.files[0])
-        if Path.is_dir(file):
-            spec = {"dir": file}
-        elif Path.is_file(file):
-            spec = {"file": file}
-        else:
-            raise SystemExit("Specified directory or file path doesn't seem to exist!")
-    else:
-        spec = {"file": [Path(f) for f in args.files]}
-    pairs = get_paired_files(parse_files(spec, just_r1=False))
+    pairs = get_paired_files(parse_files(input_spec(args.files), just_r1=False))
 
     window = int(getattr(args, "window", None) or (512 << 20))  # decoded bytes per mate per GPU pass
     if group is not None:
-        return _demux_ranks(group, args, dev, pairs, results, route_of, None if sheet else keys[fast],
-                            None if sheet else vals[fast], writers, window, level, infix, kind, sheet, lazy)
-    # with the GPU compressing, the host's cores inflate (a big single-member file in parallel); the
-    # pool's workers start at once, so the first blocks decode while the device context comes up
+        return _demux_ranks(group, args, pairs, results, route_of, table, writers, window, level, infix, kind, sheet,
+                            lazy, t_start)
     paths = [str(f) for pr in pairs for f in pr]
-    nt = _inflate_threads(kind)
-    gz = _lib.GzPool(paths, threads=nt, ahead=_lib.inflate_ahead(paths, nt))
-    STAGE_TIMES["setup: results, writers"] = time.perf_counter() - t_start
     try:
-        dmx = dev or _lib.Demux(_device_index(None))
-    except BaseException:
-        gz.close()
-        raise
-    pool = ThreadPoolExecutor(max_workers=max(2, min(32, len(writers) * 2)))
-    try:
-        if sheet is not None:
-            sheet.bind(dmx, _device_index(None), ctx)
-        else:
-            dmx.set_table(keys[fast], vals[fast])
-        STAGE_TIMES["setup"] = time.perf_counter() - t_start  # results, writers, device table, pool
-        for k, (read1_file, read2_file) in enumerate(pairs):
-            print(f"Demultiplexing {read1_file.name}...")
-            _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers, window,
-                        sheet, hit)
-        if sheet is not None and samples and not (hit & lazy):
-            print(NO_SAMPLES_WARNING)  # known only now: no pair was demuxable
+        with _session(t_start, paths, kind, len(writers), _device_index(None), sheet, table, dev, ctx,
+                      lambda: _close_writers(writers, names, lazy, hit, args.d, infix)) as (dmx, pool, gz):
+            for k, (read1_file, read2_file) in enumerate(pairs):
+                print(f"Demultiplexing {read1_file.name}...")
+                _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers,
+                            window, sheet, hit)
+            if sheet is not None and samples and not (hit & lazy):
+                print(NO_SAMPLES_WARNING)  # known only now: no pair was demuxable
     finally:
-        t_end = time.perf_counter()
-        gz.close()
-        t_gz = time.perf_counter()
-        pool.shutdown(wait=True)
-        STAGE_TIMES["finish: inflate pool"] = t_gz - t_end
-        STAGE_TIMES["finish: writer pool"] = time.perf_counter() - t_gz
-        for w in writers:
-            for f in w.values():
-                f.close()
-        _drop_unhit(names, lazy, hit, args.d, infix)
-        t_files = time.perf_counter()
-        if dev is None:
-            dmx.close()
-        elif sheet is not None:
-            dmx.set_table(np.zeros(0, np.uint64), np.zeros(0, np.int32))  # end the borrow of the sheet context
-        if sheet is not None:
-            sheet.close()
-        STAGE_TIMES["finish: files"] = t_files - t_end - STAGE_TIMES["finish: inflate pool"] - STAGE_TIMES["finish: writer pool"]
-        STAGE_TIMES["finish"] = time.perf_counter() - t_end  # last writes, closes
         STAGE_TIMES["total"] = time.perf_counter() - t_start
         if getattr(args, "stage_times", False):
             print(json.dumps({k: round(v, 3) for k, v in STAGE_TIMES.items()}), file=sys.stderr)
@@ -768,56 +754,38 @@ def _mkdir_everywhere(group, path):
         raise PeerFailed()
 
 
-def _demux_ranks(group, args, dev, pairs, results, route_of, keys, vals, names, window, level, infix, kind,
-                 sheet=None, lazy=frozenset()):
+def _demux_ranks(group, args, pairs, results, route_of, table, names, window, level, infix, kind, sheet, lazy,
+                 t_start):
     import shutil
 
     from .dist import PeerFailed, reduce_min
     rank, world = group.get_rank(), group.get_world_size()
     parts = os.path.join(args.d, ".frender-parts")
     mine = list(range(rank, len(pairs), world))
-    gz = dmx = None
-    pool = ThreadPoolExecutor(max_workers=max(2, min(32, len(names) * 2)))
     failed, exc = len(pairs), None
     try:
-        # opened inside the try: a rank whose pool or device fails still joins the collectives below
-        paths = [str(f) for k in mine for f in pairs[k]]
-        nt = _inflate_threads(kind)
-        gz = _lib.GzPool(paths, threads=nt, ahead=_lib.inflate_ahead(paths, nt))
-        dmx = _lib.Demux(_device_index(group))
-        if sheet is not None:  # this rank's own sheet context: classification is stateless, nothing is exchanged
-            sheet.bind(dmx, _device_index(group))
-        else:
-            dmx.set_table(keys, vals)
-        for j, k in enumerate(mine):
-            d = os.path.join(parts, str(k))
-            os.makedirs(d, exist_ok=True)
-            writers = [open_files(n, d, infix, level, _BgzfPart if kind is _BgzfDevice else kind) for n in names]
-            hit = set()
-            try:
-                _demux_pair(dmx, pool, gz, 2 * j, 2 * j + 1, pairs[k][0], pairs[k][1], results, route_of, writers,
-                            window, sheet, hit)
-            except (Exception, SystemExit) as e:  # re-raised below if it is the first in pair order
-                failed, exc = k, e
-            finally:
-                for w in writers:
-                    for f in w.values():
-                        f.close()
-                _drop_unhit(names, lazy, hit, d, infix)  # -b: no part for a sample this pair has no reads of
-            if exc is not None:
-                break
+        # the session opens inside the try: a rank whose pool or device fails still joins the collectives below
+        # (-b: this rank's own sheet context: classification is stateless, nothing is exchanged)
+        with _session(t_start, [str(f) for k in mine for f in pairs[k]], kind, len(names), _device_index(group),
+                      sheet, table) as (dmx, pool, gz):
+            for j, k in enumerate(mine):
+                d = os.path.join(parts, str(k))
+                os.makedirs(d, exist_ok=True)
+                writers = [open_files(n, d, infix, level, _BgzfPart if kind is _BgzfDevice else kind) for n in names]
+                hit = set()
+                try:
+                    _demux_pair(dmx, pool, gz, 2 * j, 2 * j + 1, pairs[k][0], pairs[k][1], results, route_of, writers,
+                                window, sheet, hit)
+                except (Exception, SystemExit) as e:  # re-raised below if it is the first in pair order
+                    failed, exc = k, e
+                finally:
+                    _close_writers(writers, names, lazy, hit, d, infix)  # -b: no part for a sample without reads here
+                if exc is not None:
+                    break
     except (Exception, SystemExit) as e:  # before any pair (the device, the table): this rank's first pair
         if exc is None:
             failed, exc = (mine[0] if mine else len(pairs)), e
-    finally:
-        pool.shutdown(wait=True)
-        if gz is not None:
-            gz.close()
-        if dmx is not None:
-            dmx.close()
-        if sheet is not None:
-            sheet.close()
-    first = int(reduce_min(group, _wire(group), [failed])[0])  # every rank's pairs are done here
+    first =int(reduce_min(group, _wire(group), [failed])[0])  # every rank's pairs are done here
     last = min(first, len(pairs) - 1)
     if rank == 0:
         for k in range(last + 1):

@@ -102,6 +102,19 @@ def get_indexes(barcode_file, single: bool = False) -> dict:
         return out
 
 
+def input_spec(files_arg) -> dict:
+    """frender.py:587-599, :759-771: the positional arguments as parse_files takes them.  One argument is a
+    directory or a file, and has to exist; several are a list of files."""
+    if len(files_arg) != 1:
+        return {"file": [Path(f) for f in files_arg]}
+    p = Path(files_arg[0])
+    if Path.is_dir(p):
+        return {"dir": p}
+    if Path.is_file(p):
+        return {"file": p}
+    raise SystemExit("Specified directory or file path doesn't seem to exist!")
+
+
 def parse_files(file_dict: dict, just_r1: bool) -> list:
     """frender.py:119-151 — the input order defines the output row order (R5)."""
     kind = list(file_dict.keys())[0]

@@ -33,8 +33,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import (SINGLE_RC_REFUSAL, find_barcode_file, get_cores, get_indexes, parse_files, reverse_complement,
-                   single_index)
+from .host import (SINGLE_RC_REFUSAL, find_barcode_file, get_cores, get_indexes, input_spec, parse_files,
+                   reverse_complement, single_index)
 
 UNDET, HOP, DEMUX, AMBIG = 0, 1, 2, 3
 CLASS_NAMES = _lib.CLASS_NAMES
@@ -317,6 +317,38 @@ def _lead(table) -> bool:
     return table.group is None or table.group.get_rank() == 0
 
 
+def upload_sheet(ctx, indexes, single: bool = False) -> tuple:
+    """The sample sheet onto ctx, for `scan` and for `demux -b` alike: (idx1, idx2, ids, names, name_id) as
+    uploaded.  indexes: get_indexes' dict, or the (idx1, idx2, ids) lists.  single (--single-index): every
+    idx2 is the empty string, and the context is put into that index mode (back into the dual one otherwise)."""
+    if isinstance(indexes, dict):
+        indexes = indexes["idx1"], indexes["idx2"], indexes["id"]
+    idx1, idx2, ids = (list(x) for x in indexes)
+    if single:
+        idx2 = [""] * len(idx1)
+    if single != getattr(ctx, "single_index", False):
+        ctx.set_index_mode(single)
+    names, name_id = _sheet_names(ids)
+    ctx.set_sheet(idx1, idx2, [reverse_complement(x) for x in idx2], name_id, len(names))
+    return idx1, idx2, ids, names, name_id
+
+
+def split_exotic(codes, single: bool = False) -> tuple:
+    """The exotic-code rule, ahead of classify_cp: (kept, q1, q2, bare).  A code is split at
+    '+' and case-folded: codes[kept[k]] is classified as (q1[k], q2[k]), its first two parts.  A code without
+    '+' is error 3 (positions `bare`, not kept) unless single, where every code is kept with q2 = ""."""
+    kept, q1, q2, bare = [], [], [], []
+    for k, c in enumerate(codes):
+        parts = c.split("+")
+        if len(parts) < 2 and not single:
+            bare.append(k)
+            continue
+        kept.append(k)
+        q1.append(parts[0].lower())
+        q2.append("" if single else parts[1].lower())
+    return kept, q1, q2, bare
+
+
 def process(cores, table: UniqueTable, indexes: dict, num_subs: int, rc_mode: bool, ctx=None,
             single: bool = False) -> Results:
     """frender.py:391-426 on the GPU: classify every unique code (fast keys by packed
@@ -327,15 +359,9 @@ def process(cores, table: UniqueTable, indexes: dict, num_subs: int, rc_mode: bo
     reference classifies idx1 + "+" against a sheet whose idx2 are all "" (DESIGN.md §4.4); only idx1's
     length can be in error, and there is no -rc."""
     ctx = ctx or default_context()
-    idx1, idx2, ids = list(indexes["idx1"]), list(indexes["idx2"]), list(indexes["id"])
-    if single:
-        if rc_mode:
-            raise SystemExit(SINGLE_RC_REFUSAL)
-        idx2 = [""] * len(idx1)
-    if single != getattr(ctx, "single_index", False):
-        ctx.set_index_mode(single)
-    names, name_id = _sheet_names(ids)
-    ctx.set_sheet(idx1, idx2, [reverse_complement(x) for x in idx2], name_id, len(names))
+    if single and rc_mode:
+        raise SystemExit(SINGLE_RC_REFUSAL)
+    idx1, idx2, ids, names, name_id = upload_sheet(ctx, indexes, single)
     if cores > 1 and _lead(table):
         print(f"Multiprocessing with {cores} cores")
     n = len(table)
@@ -357,15 +383,10 @@ def process(cores, table: UniqueTable, indexes: dict, num_subs: int, rc_mode: bo
     f_add = np.zeros(len(names), np.uint64)
     r_add = np.zeros(len(names), np.uint64)
     if esel.size:
-        split_ok, q1, q2, js = [], [], [], []
-        for j in esel.tolist():
-            parts = table.codes[j].split("+")
-            if len(parts) < 2 and not single:
-                errs.append((j, 3))
-                continue
-            js.append(j)
-            q1.append(parts[0].lower())
-            q2.append("" if single else parts[1].lower())
+        exo = esel.tolist()
+        kept, q1, q2, bare = split_exotic([table.codes[j] for j in exo], single)
+        errs += [(exo[k], 3) for k in bare]
+        js = [exo[k] for k in kept]
         if js:
             out = ctx.classify_cp(q1, q2, num_subs, rc_mode)
             ja = np.array(js)
@@ -646,17 +667,13 @@ def report_analysis(table: UniqueTable, results: Results, demux_ok, out_csv_name
 
 def output_name(num_subs, user_infix, files_arg):
     """frender.py:587-601."""
-    if len(files_arg) == 1:
-        p = Path(files_arg[0])
-        if Path.is_dir(p):
-            spec, tail = {"dir": p}, p.parts[-1]
-        elif Path.is_file(p):
-            spec, tail = {"file": p}, p.name
-        else:
-            raise SystemExit("Specified directory or file path doesn't seem to exist!")
-    else:
-        spec = {"file": [Path(f) for f in files_arg]}
+    spec = input_spec(files_arg)
+    if "dir" in spec:
+        tail = spec["dir"].parts[-1]
+    elif isinstance(spec["file"], list):
         tail = datetime.strftime(datetime.now(timezone.utc), "%Y-%M-%d_%H%M_%Z")
+    else:
+        tail = spec["file"].name
     return f"frender-scan-results_{num_subs}-mismatches_{user_infix}_{tail}.csv".replace("__", "_"), spec
 
 

@@ -22,6 +22,29 @@ def case_names():
     return sorted(os.listdir(CASES)) if os.path.isdir(CASES) else []
 
 
+def compare_outputs(exp_dir, tmp, stdout, want_err) -> list:
+    """The differences between a run in `tmp` (its stdout; its files under tmp/out) and the case's expected
+    stdout and, unless the case expects an error, output files: their names and their decoded contents."""
+    diffs = []
+    want_out = open(os.path.join(exp_dir, "stdout.txt")).read()
+    if stdout.replace(tmp, "<case>") != want_out:
+        diffs.append(f"stdout: got {stdout!r} want {want_out!r}")
+    if want_err is None:
+        outd = os.path.join(tmp, "out")
+        got = sorted(os.listdir(outd)) if os.path.isdir(outd) else []
+        want = sorted(f[:-len(".content.gz")] for f in os.listdir(exp_dir) if f.endswith(".content.gz"))
+        if got != want:
+            diffs.append(f"output files: got {got} want {want}")
+        for fn in set(got) & set(want):
+            with gzip.open(os.path.join(outd, fn), "rb") as g:
+                a = g.read()
+            with gzip.open(os.path.join(exp_dir, fn + ".content.gz"), "rb") as g:
+                b = g.read()
+            if a != b:
+                diffs.append(f"{fn}: content differs ({len(a)} vs {len(b)} bytes)")
+    return diffs
+
+
 def run_case(name, demux_fn):
     """Run demux_fn(args) on the case's inputs; return a list of differences (empty = parity)."""
     case = os.path.join(CASES, name)
@@ -50,22 +73,7 @@ def run_case(name, demux_fn):
             want_err = json.load(open(os.path.join(exp_dir, "error.json")))
         if err != want_err:
             diffs.append(f"error: got {err} want {want_err}")
-        want_out = open(os.path.join(exp_dir, "stdout.txt")).read()
-        if buf.getvalue().replace(tmp, "<case>") != want_out:
-            diffs.append(f"stdout: got {buf.getvalue()!r} want {want_out!r}")
-        if want_err is None:
-            outd = os.path.join(tmp, "out")
-            got = sorted(os.listdir(outd)) if os.path.isdir(outd) else []
-            want = sorted(f[:-len(".content.gz")] for f in os.listdir(exp_dir) if f.endswith(".content.gz"))
-            if got != want:
-                diffs.append(f"output files: got {got} want {want}")
-            for fn in set(got) & set(want):
-                with gzip.open(os.path.join(outd, fn), "rb") as g:
-                    a = g.read()
-                with gzip.open(os.path.join(exp_dir, fn + ".content.gz"), "rb") as g:
-                    b = g.read()
-                if a != b:
-                    diffs.append(f"{fn}: content differs ({len(a)} vs {len(b)} bytes)")
+        diffs += compare_outputs(exp_dir, tmp, buf.getvalue(), want_err)
     return diffs
 
 
@@ -99,21 +107,6 @@ def run_case_cli(name, gpus=2):
             diffs.append(f"exit {r.returncode}: {r.stderr[-1500:]}")
         if want_err is not None and (not r.returncode or want_err["message"].replace("<case>", tmp) not in r.stderr):
             diffs.append(f"error: want {want_err}, exit {r.returncode}, stderr {r.stderr[-1500:]}")
-        want_out = open(os.path.join(exp_dir, "stdout.txt")).read()
         out = "".join(ln for ln in r.stdout.splitlines(True) if not ln.startswith("[Gloo]"))  # gloo's banner
-        if out.replace(tmp, "<case>") != want_out:
-            diffs.append(f"stdout: got {out!r} want {want_out!r}")
-        if want_err is None:
-            outd = os.path.join(tmp, "out")
-            got = sorted(os.listdir(outd)) if os.path.isdir(outd) else []
-            want = sorted(f[:-len(".content.gz")] for f in os.listdir(exp_dir) if f.endswith(".content.gz"))
-            if got != want:
-                diffs.append(f"output files: got {got} want {want}")
-            for fn in set(got) & set(want):
-                with gzip.open(os.path.join(outd, fn), "rb") as g:
-                    a = g.read()
-                with gzip.open(os.path.join(exp_dir, fn + ".content.gz"), "rb") as g:
-                    b = g.read()
-                if a != b:
-                    diffs.append(f"{fn}: content differs ({len(a)} vs {len(b)} bytes)")
+        diffs += compare_outputs(exp_dir, tmp, out, want_err)
     return diffs

@@ -74,9 +74,9 @@ def test_writer_appends_runs_and_one_eof_block(tmp_path):
     cut = 7 + len(expected(d1))
     for kind, tail in ((_BgzfDevice, EOF), (_BgzfPart, b"")):
         w = kind(str(tmp_path / "a.fq.gz"), 9)
-        w.write_members(runs, 7, cut)
-        w.write_members(runs, cut, cut)  # an empty run writes nothing
-        w.write_members(runs, cut, runs.size)
+        w.write(runs, 7, cut)
+        w.write(runs, cut, cut)  # an empty run writes nothing
+        w.write(runs, cut, runs.size)
         w.close()
         blob = (tmp_path / "a.fq.gz").read_bytes()
         assert blob == expected(d1) + expected(d2) + tail
