@@ -286,8 +286,90 @@ __device__ FR_COLD void direct_insert(ScanShared& sh, const ScanArgs& a, u64 key
 
 __device__ __forceinline__ void rare_push(ScanShared& sh, const ScanArgs& a, u32 p, u32 kind, u32 x, u32 y);
 
+// An LDS-table miss of the tile loop, held in the lane until the next tile's top (walk_wave): gfx950 counts
+// stores and loads in one vmcnt, so a cold-list store issued after the next tile's loads is waited for, up to
+// its acknowledge from L2, at the loop-top wait for those loads.  Flushed ahead of them it has a wave-tile's
+// time to drain.
+constexpr u32 COLD_NONE = 0xFFFFFFFFu;
+struct ColdPend {
+    u64 key;
+    u32 off;  // the record's chunk offset, COLD_NONE: nothing pending
+};
+
+// what a cold-list entry needs beside the miss itself; none of it changes during a walk
+typedef __attribute__((address_space(1))) u32x4 global_u32x4;  // a global (not flat) store, whatever the optimizer infers
+struct ColdDest {
+    global_u32x4* list;  // this workgroup's cold list
+    u32 cap;
+    u64 obase;    // file offset of the chunk's first byte: an entry's ordinal is tag | (obase + off) & ~3 (make_ord)
+    u64 tag;      // file tag << ORD_SHIFT
+};
+
+__device__ __forceinline__ u32 uniform32(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ u64 uniform64(u64 v) {
+    return ((u64)uniform32((u32)(v >> 32)) << 32) | uniform32((u32)v);
+}
+
+__device__ __forceinline__ ColdDest cold_dest(const ScanShared& sh, const ScanArgs& a) {
+    ColdDest d;
+    d.cap = uniform32(a.cold_cap);
+    d.list = (global_u32x4*)uniform64((u64)(a.cold + 2ull * ((u64)blockIdx.x * d.cap)));
+    d.obase = uniform64(a.file_offset + sh.cbase);
+    d.tag = (u64)uniform32(a.file_tag) << ORD_SHIFT;
+    return d;
+}
+
+// Park one LDS-table miss in the workgroup's cold list (committed with the chunk), in two steps: claim the
+// entry's index i, then one 16-byte store {key, ordinal} (the list is 16-byte aligned: hipMalloc, 16-byte
+// entries).  A full list: the chunk is redone exactly when it speculates, else the insert goes to the HBM table,
+// directly from drain_rare or queued for it from the tile loop.
+__device__ __forceinline__ u32 cold_claim(ScanShared& sh) { return atomicAdd(&sh.ncold, 1u); }
+
+template <bool DRAIN>
+__device__ __forceinline__ void cold_put_at(ScanShared& sh, const ScanArgs& a, const ColdDest& d, u64 key, u32 off,
+                                            u32 i) {
+    if (i < d.cap) {
+        const u64 ord = d.tag | ((d.obase + off) & ~3ull);
+        // ablation 16: the context's first three launches fill the lists, later ones leave them as they are
+        if (!(ABLATE & 16u) || a.epoch <= 3u) d.list[i] = u32x4{(u32)key, (u32)(key >> 32), (u32)ord, (u32)(ord >> 32)};
+        else asm volatile("" ::"v"(ord), "v"(key));
+        return;
+    }
+    if (sh.spec) {  // cannot insert while speculating: this chunk will be redone exactly
+        atomicOr(&sh.spec_bad, 1u);
+        return;
+    }
+    // exact phase and a full cold list: insert directly (queued out of the hot loop)
+    if (DRAIN) direct_insert(sh, a, key, off);
+    else rare_push(sh, a, off, 3u, (u32)key, (u32)(key >> 32));
+}
+
+template <bool DRAIN>
+__device__ __forceinline__ void cold_put(ScanShared& sh, const ScanArgs& a, const ColdDest& d, u64 key, u32 off) {
+    cold_put_at<DRAIN>(sh, a, d, key, off, cold_claim(sh));
+}
+
+// The lanes' pending misses, if any, go to the cold list; the whole wave calls both halves, and a scalar branch
+// skips them when no lane holds a miss.  walk_wave claims before the tile copy and stores after it, so the LDS
+// atomic's round trip passes under the copy's four ds_write_b128 instead of behind them.
+__device__ __forceinline__ bool cold_flush_claim(ScanShared& sh, const ColdPend& pd, u32& i) {
+    const bool any = __ballot(pd.off != COLD_NONE) != 0;
+    i = 0;
+    if (any && pd.off != COLD_NONE) i = cold_claim(sh);
+    return any;
+}
+__device__ __forceinline__ void cold_flush_store(ScanShared& sh, const ScanArgs& a, const ColdDest& d, ColdPend& pd,
+                                                 bool any, u32 i) {
+    if (!any) return;
+    if (pd.off != COLD_NONE) cold_put_at<false>(sh, a, d, pd.key, pd.off, i);
+    pd.off = COLD_NONE;
+}
+
+// DRAIN (drain_rare's paths): a miss is stored at once.  Otherwise (the tile loop) it stays pending in pd, and a
+// lane that already holds one (a second header in its segment: records shorter than 64 B) stores the older first.
 template <bool DRAIN = false>
-__device__ __forceinline__ void lds_insert(ScanShared& sh, const ScanArgs& a, u64 key, u32 off) {
+__device__ __forceinline__ void lds_insert(ScanShared& sh, const ScanArgs& a, u64 key, u32 off, const ColdDest* d,
+                                           ColdPend* pd) {
     // one 32-bit multiply (keys hold <= 63 bits: fold the top down first)
     u32 h = (((u32)key ^ (u32)(key >> 27)) * 0x9E3779B1u) >> (32 - LOG_NS);
 #pragma unroll 2
@@ -321,21 +403,14 @@ __device__ __forceinline__ void lds_insert(ScanShared& sh, const ScanArgs& a, u6
         }
         h = (h + 1) & (NS - 1);
     }
-    // an LDS-table miss: park it in this workgroup's cold list (committed with the chunk)
-    const u32 i = atomicAdd(&sh.ncold, 1u);
-    if (i < a.cold_cap) {
-        u64* c = a.cold + 2ull * ((u64)blockIdx.x * a.cold_cap + i);
-        c[0] = key;
-        c[1] = make_ord(a, sh.cbase + off);
-        return;
+    // an LDS-table miss
+    if (DRAIN) {
+        cold_put<true>(sh, a, cold_dest(sh, a), key, off);
+    } else {
+        if (pd->off != COLD_NONE) cold_put<false>(sh, a, *d, pd->key, pd->off);
+        pd->key = key;
+        pd->off = off;
     }
-    if (sh.spec) {  // cannot insert while speculating: this chunk will be redone exactly
-        atomicOr(&sh.spec_bad, 1u);
-        return;
-    }
-    // exact phase and a full cold list: insert directly (queued out of the hot loop)
-    if (DRAIN) direct_insert(sh, a, key, off);
-    else rare_push(sh, a, off, 3u, (u32)key, (u32)(key >> 32));
 }
 
 // Rare events (exotic codes, headers without ' ', headers whose code leaves the bitmap window,
@@ -454,13 +529,15 @@ __device__ FR_COLD bool utf8_segment_ok(const ScanArgs& a, u64 s0, u32 n) {
     return true;
 }
 
+// d, pd: the tile loop's (DRAIN = false) cold-list destination and the lane's pending miss
 template <bool DRAIN = false>
-__device__ __forceinline__ void count_code(ScanShared& sh, const ScanArgs& a, u32 p, u64 key) {
+__device__ __forceinline__ void count_code(ScanShared& sh, const ScanArgs& a, u32 p, u64 key,
+                                           const ColdDest* d = nullptr, ColdPend* pd = nullptr) {
     if ((ABLATE & 4u) || a.exo_only) {  // ablation / exotic-only replay: skip the hash insert
         asm volatile("" ::"v"(key));
         return;
     }
-    lds_insert<DRAIN>(sh, a, key, p);
+    lds_insert<DRAIN>(sh, a, key, p, d, pd);
 }
 
 // code bytes [q, q+n) of the range (exact byte reads) -> wide key (fr_internal.h), false when the
@@ -1400,7 +1477,8 @@ __device__ __forceinline__ int locate_near(const ScanShared& sh, u32 wid, u32 p,
     return (p >= bl || se == 0ull) ? 2 : (se1 == 0ull ? 3 : 0);
 }
 
-__device__ __forceinline__ void parse_header(ScanShared& sh, const ScanArgs& a, u32 wid, u32 tile0, u32 p, u32 bl) {
+__device__ __forceinline__ void parse_header(ScanShared& sh, const ScanArgs& a, u32 wid, u32 tile0, u32 p, u32 bl,
+                                             const ColdDest& cd, ColdPend& pd) {
     u32 start = 0, n = 0, f1 = 0;
     int r = locate_near(sh, wid, p, bl, start, n, f1);
     if (__ballot(r == 3) != 0) {  // uniform: some lane's token ends past its first window
@@ -1431,7 +1509,7 @@ __device__ __forceinline__ void parse_header(ScanShared& sh, const ScanArgs& a, 
         r = 1;
         fast = false;
     }
-    if (fast) count_code(sh, a, tile0 + p, key);
+    if (fast) count_code(sh, a, tile0 + p, key, &cd, &pd);
     else rare_push(sh, a, tile0 + p, (u32)r, tile0 + start, n);
 }
 
@@ -1441,7 +1519,8 @@ __device__ __forceinline__ void parse_header(ScanShared& sh, const ScanArgs& a, 
 // (records shorter than 64 B) takes the loop at the end.
 template <bool LIM>
 __device__ __forceinline__ void parse_own_headers(ScanShared& sh, const ScanArgs& a, u32 t, u32 ct,
-                                                  const SegClass& sc, u64 L0, int lane, u32 wid) {
+                                                  const SegClass& sc, u64 L0, int lane, u32 wid, const ColdDest& cd,
+                                                  ColdPend& pd) {
     const u64 tile0 = (u64)t * TSTEP;
     const u32 tile0c = (t - ct) * TSTEP;  // the tile's chunk offset (ct: the chunk's first tile)
     const u32 bl = (u32)min((u64)TILE, a.avail - tile0);
@@ -1466,7 +1545,7 @@ __device__ __forceinline__ void parse_own_headers(ScanShared& sh, const ScanArgs
     // m's lowest set bit: the first header terminator.  own0's header at position 0 comes first.
     const u32 p = own0 ? 0u : s0 + ctz64x(m) + 1u;
     const bool ok = own0 || (m != 0 && p < pend && (!limited || (i64)rec < a.max_records));
-    if (ok) parse_header(sh, a, wid, tile0c, p, bl);
+    if (ok) parse_header(sh, a, wid, tile0c, p, bl, cd, pd);
     // another header in this segment (records shorter than 64 B; never at R=8's 74 B): uniform check
     bool more = ok && (own0 ? m != 0 : __popcll(m) > 4);
     if (!__ballot(more)) return;
@@ -1481,7 +1560,7 @@ __device__ __forceinline__ void parse_own_headers(ScanShared& sh, const ScanArgs
         if (more) {
             const u32 pn = s0 + ctz64x(m) + 1u;
             more = pn < pend && (!limited || (i64)rec < a.max_records);
-            if (more) parse_header(sh, a, wid, tile0c, pn, bl);
+            if (more) parse_header(sh, a, wid, tile0c, pn, bl, cd, pd);
             ++rec;
             m &= m - 1ull;
             m &= m - 1ull;
@@ -1497,7 +1576,8 @@ __device__ __forceinline__ void parse_own_headers(ScanShared& sh, const ScanArgs
 // workgroup barrier: every LDS area the walk writes is this wave's.  Per step: the tile's bytes
 // (in registers since the previous step) go to the wave's LDS copy first, so the registers take the
 // next tile's loads at once and those stay in flight through this tile's classify AND its parse;
-// the classify reads the lane's segment back from LDS.
+// the classify reads the lane's segment back from LDS.  A lane's LDS-table miss of tile t waits in registers (pd)
+// and is stored to the cold list at the top of step t + 1, ahead of that step's loads, or after the loop.
 template <bool LIM>
 __device__ __forceinline__ u64 walk_wave(ScanShared& sh, const ScanArgs& a0, u32 ct, u32 tb, u32 te, u64 L0,
                                          bool parse, int lane, u32 wid) {
@@ -1507,6 +1587,8 @@ __device__ __forceinline__ u64 walk_wave(ScanShared& sh, const ScanArgs& a0, u32
     SegRegs r;
     if (tb < te) seg_load(a, tb, r, lane);
     lds_u32x4* mine = (lds_u32x4*)(&sh.raw[wid][0]) + lane * (SEG / 16);
+    const ColdDest cd = cold_dest(sh, a);  // once per walk
+    ColdPend pd = {0ull, COLD_NONE};
     FR_WSTAMP_DECL
     for (u32 t = tb; t < te; ++t) {
 #if defined(FR_STAMPS) && FR_STAMPS == 4
@@ -1514,6 +1596,9 @@ __device__ __forceinline__ u64 walk_wave(ScanShared& sh, const ScanArgs& a0, u32
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         FR_WSTAMP(0);
 #endif
+        // the previous tile's LDS-table misses: their cold-list indices are claimed here, ahead of the copy
+        u32 ci;
+        const bool cany = cold_flush_claim(sh, pd, ci);
         // the previous tile's parse is done with the LDS copy (program order)
 #pragma unroll
         for (int k = 0; k < SEG / 16; ++k) {
@@ -1521,6 +1606,9 @@ __device__ __forceinline__ u64 walk_wave(ScanShared& sh, const ScanArgs& a0, u32
             v.x = r.v[k].x; v.y = r.v[k].y; v.z = r.v[k].z; v.w = r.v[k].w;
             mine[k] = v;
         }
+        // ... and their stores go out ahead of the next tile's loads: the loop-top wait for those loads then has
+        // no younger store to wait for
+        cold_flush_store(sh, a, cd, pd, cany, ci);
         if (t + 1 < te) seg_load(a, t + 1, r, lane);
         // volatile: a real LDS read, one quarter of the segment at a time inside the classify
         const SegClass sc = seg_classify_src(a, t, [&](int k) {
@@ -1543,11 +1631,14 @@ __device__ __forceinline__ u64 walk_wave(ScanShared& sh, const ScanArgs& a0, u32
         // redone exactly and everything its walk buffered is discarded, so parsing on is harmless; the check
         // was an LDS round trip per tile)
         FR_WSTAMP(2);
-        if (parse && !(ABLATE & 1u)) parse_own_headers<LIM>(sh, a, t, ct, sc, L0 + lines, lane, wid);
+        if (parse && !(ABLATE & 1u)) parse_own_headers<LIM>(sh, a, t, ct, sc, L0 + lines, lane, wid, cd, pd);
         lines += sc.wtot;
         FR_WSTAMP(3);
     }
     FR_WSTAMP_FLUSH(te > tb ? te - tb : 0u);
+    u32 ci;  // the last tile's misses: everything the walk buffers is in place when it returns
+    const bool cany = cold_flush_claim(sh, pd, ci);
+    cold_flush_store(sh, a, cd, pd, cany, ci);
     lds_fence();
     const u32 tail = *(const volatile lds_u32*)&sh.rq_tail[wid];
     if (tail != done) drain_rare(sh, a, wid, done, tail, lane);

@@ -7,7 +7,8 @@ namespace fr {
 
 // Timing ablations exist only in experiment builds: scripts/build_exp.sh NAME
 // "-DFR_ABLATE=<bits>" (1 no header parse, 2 no code encode, 4 no LDS insert, 8 no commit flush,
-// 64 commit counts, 128 plain stores in the commit (wrong counts), 256/512/1024/2048 launch-log passes).
+// 16 no cold-list entry stores after the context's third launch (the commits read the entries those left: wrong
+// counts), 64 commit counts, 128 plain stores in the commit (wrong counts), 256/512/1024/2048 launch-log passes).
 // The product build has FR_ABLATE = 0: every ablation branch folds away at compile time, and nothing
 // read at run time (no environment variable, no kernel argument) can select one.
 #ifndef FR_ABLATE

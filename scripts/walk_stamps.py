@@ -1,6 +1,7 @@
 """Where a wave's time goes in the tally's walk (diagnostic; FR_STAMPS=4 build: scripts/build_exp.sh ws
-"-DFR_STAMPS=4").  Per wave, walk_wave adds s_memtime cycles of: 0 the wait for the tile's VMEM loads, 1 the
-LDS copy + classify (its LDS read-back included), 2 the rare-event drain + bitmap stores + LDS fence, 3 the
+"-DFR_STAMPS=4").  Per wave, walk_wave adds s_memtime cycles of: 0 the loop-top wait (vmcnt(0): every vector-memory operation
+outstanding there, the tile's loads and any store issued after them), 1 the cold-list flush + LDS copy +
+classify (its LDS read-back included), 2 the rare-event drain + bitmap stores + LDS fence, 3 the
 header parse; 4 counts walk steps, 5 sums whole-kernel wave cycles, 6 counts walk calls.  The stamps cost
 time themselves (their s_memtime waits on lgkmcnt): read the shares, not the absolute kernel time.
 usage: FRENDER_HIP_LIB=frender_amd/libfrender_hip_exp_ws.so python scripts/walk_stamps.py [out.json]
