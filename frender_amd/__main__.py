@@ -71,6 +71,13 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("-n", metavar="[int]", type=int,
                    help="with -b (required there, rejected with -r): number of mismatches allowed between the "
                         "sheet's barcodes and the reads', as scan's -n")
+    d.add_argument("--report", metavar="results_csv",
+                   help="with -b: also write the results CSV that `scan -n N -b` writes for the pairs' read 1 files "
+                        "(every distinct code with its reads, class, sample and demux_ok), counted in the same "
+                        "pass")
+    d.add_argument("-p", metavar="fix_prefix",
+                   help="with --report: when matching sample ids to filenames for demux_ok, remove this prefix from "
+                        "the sample id (scan's -p)")
     d.add_argument("--strict-header", action="store_true",
                    help="reject a results file in scan's own column order, as frender.py does (default: accept it)")
     d.add_argument("--gz-level", type=int, default=None,
@@ -116,9 +123,10 @@ def main(argv=None):
         frender_scan(args)
         return 0
     if getattr(args, "cmd", None) == "demux":
-        from .host import demux_mode, gz_format
+        from .host import demux_mode, gz_format, report_args
         try:
             demux_mode(args)  # -r or -b with -n, before ranks start (frender_demux checks it too)
+            report_args(args)  # --report with -b, -p with --report
         except SystemExit as e:
             parser.error(str(e))
         gz_format(args)  # a bad writer/format pair ends here, before ranks start (frender_demux checks it too)

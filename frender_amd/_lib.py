@@ -160,6 +160,12 @@ _SIGS = {
     "fr_dmx_deflate": (C.c_int, [P, C.c_int, C.c_int, P, P]),
     "fr_dmx_fetch_deflated": (C.c_int, [P, C.c_int, P, C.c_uint64]),
     "fr_dmx_deflate_bgzf": (C.c_int, [P, C.c_int, C.c_int, P]),
+    "fr_dmx_tally_begin": (C.c_int, [P, C.c_uint64]),
+    "fr_dmx_tally_file": (C.c_int, [P, C.c_int64]),
+    "fr_dmx_tally_window": (C.c_int, [P, C.c_uint64, C.c_uint64]),
+    "fr_dmx_tally_sizes": (C.c_int, [P, u64p, u64p]),
+    "fr_dmx_tally_get": (C.c_int, [P, P, P, P, P, P, P]),
+    "fr_dmx_tally_rows_device": (C.c_int, [P, P, C.c_uint64]),
     "fr_defl_create": (P, [C.c_int]),
     "fr_defl_destroy": (None, [P]),
     "fr_defl_last_error": (C.c_char_p, [P]),
@@ -569,6 +575,36 @@ class Demux:
         out = np.empty(int(comp.sum()), np.uint8)
         self._ck(lib.fr_dmx_fetch_deflated(self.h, mate, _ptr(out), out.size), "fr_dmx_fetch_deflated")
         return comp, out
+
+    # ---- the windows' tally (demux -b --report; fr_dmx_tally_*) ---------------------------
+    def tally_begin(self, initial_slots: int = 0):
+        self._ck(lib.fr_dmx_tally_begin(self.h, int(initial_slots)), "fr_dmx_tally_begin")
+
+    def tally_file(self, file_index: int):
+        self._ck(lib.fr_dmx_tally_file(self.h, int(file_index)), "fr_dmx_tally_file")
+
+    def tally_window(self, n_pairs: int, first_record: int):
+        """Count the n_pairs records the last route() routed; first_record: the first one's index in its pair."""
+        self._ck(lib.fr_dmx_tally_window(self.h, int(n_pairs), int(first_record)), "fr_dmx_tally_window")
+
+    def tally_sizes(self) -> tuple:
+        u, p = C.c_uint64(), C.c_uint64()
+        self._ck(lib.fr_dmx_tally_sizes(self.h, C.byref(u), C.byref(p)), "fr_dmx_tally_sizes")
+        return u.value, p.value
+
+    def tally_get(self) -> dict:
+        """The tally as host arrays, in no fixed order: keys, counts, first per code, and (pu, pf, pn) = (index in
+        keys, file index, reads) per code and file pair."""
+        n, m = self.tally_sizes()
+        out = {"keys": np.empty(n, np.uint64), "counts": np.empty(n, np.uint64), "first": np.empty(n, np.uint64),
+               "pu": np.empty(m, np.uint32), "pf": np.empty(m, np.uint32), "pn": np.empty(m, np.uint64)}
+        self._ck(lib.fr_dmx_tally_get(self.h, *(_ptr(out[k]) for k in ("keys", "counts", "first", "pu", "pf", "pn"))),
+                 "fr_dmx_tally_get")
+        return out
+
+    def tally_rows_device(self, dev_ptr: int, cap: int):
+        """The tally's (key, count, first) rows as int64 [n][3] at dev_ptr (cap rows): Context.merge_rows_at's form."""
+        self._ck(lib.fr_dmx_tally_rows_device(self.h, P(dev_ptr), int(cap)), "fr_dmx_tally_rows_device")
 
 
 class Deflater:
@@ -1040,6 +1076,15 @@ class Context:
         torch.cuda.current_stream(rows.device).synchronize()
         self._ck(lib.fr_merge_rows_device(self.h, P(rows.data_ptr()), n), "fr_merge_rows_device")
         self.sync()  # rows goes back to torch's allocator after this
+
+    def merge_rows_at(self, dev_ptr: int, n: int, step: int = 1 << 20):
+        """Merge n (key, count, first) int64 rows at dev_ptr (this GPU's memory, row-major, complete) into the
+        table (fr_merge_rows_device), without PyTorch.  In steps: the rows a merge cannot place at once wait
+        in the overflow list (fr_tuning.ovf_cap, 4 Mi entries) until the table has grown."""
+        for o in range(0, int(n), step):
+            self._ck(lib.fr_merge_rows_device(self.h, P(dev_ptr + 24 * o), min(step, int(n) - o)),
+                     "fr_merge_rows_device")
+        self.sync()
 
     # ---- tensor views for the multi-GPU merge (frender_amd/dist.py) ----------------------
     def export_rows(self, device):

@@ -13,6 +13,8 @@
 //   route      stable partition of the record pairs by destination (rocprim radix sort on the
 //              destination, record index as payload), output offsets (rocprim scans) and a
 //              gather-copy of both mates' record bytes into destination-major buffers
+// With fr_dmx_tally_begin (sheet mode, `demux -b --report`) the routed records' keys are also counted: the kernels
+// and their tables are fr_dmx_tally.hip's, the entry points at the end of this file check mode and call order.
 // The host inflates, normalises universal newlines (frender.py:776 reads in text mode), resolves
 // the rare codes outside the fast alphabet, raises the reference's errors, and gzips each
 // destination's bytes into its writer pair.
@@ -399,6 +401,10 @@ struct fr_dmx {
     u64 out_len[2] = {0, 0};
     std::vector<u64> hoff[2];  // destination offsets of the routed bytes (host copy)
     fr_defl* defl[2] = {nullptr, nullptr};  // the writers' compression (fr_deflate.hip), created on first use
+    // the windows' tally (fr_dmx_tally_begin; fr_dmx_tally.hip), and the pairs the last fr_dmx_route routed that
+    // no fr_dmx_tally_window has counted yet
+    DmxTally* tally = nullptr;
+    u64 routed_ok = 0;
 };
 
 #define DK(x)                                                                  \
@@ -442,6 +448,7 @@ void fr_dmx_destroy(fr_dmx* d) {
     for (void* x : p)
         if (x) (void)hipFree(x);
     for (fr_defl* z : d->defl) fr_defl_destroy(z);
+    dmx_tally_destroy(d->tally);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
 }
@@ -508,6 +515,7 @@ int fr_dmx_set_sheet(fr_dmx* d, fr_ctx* ctx, int num_subs, const int32_t* row_de
 static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_records) {
     d->src[mate] = buf;
     d->len[mate] = len;
+    d->routed_ok = 0;
     const u32 ntiles = (u32)((len + DT - 1) / DT);
     DK(ensure(&d->cnt, d->c_cnt, (u64)ntiles + 1));
     DK(ensure(&d->base, d->c_base, (u64)ntiles + 1));
@@ -644,6 +652,7 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     if (P >= 0xFFFFFFFFull) return d->err = "too many records in one file pair", FR_ERR_CAPACITY;
     *first_error = -1;
     *error_val = 0;
+    d->routed_ok = 0;
     for (int k = 0; k < n_dest; ++k) bytes_r1[k] = bytes_r2[k] = 0;
     d->out_len[0] = d->out_len[1] = 0;
     d->hoff[0].assign((size_t)std::max(n_dest, 0) + 1, 0);
@@ -720,7 +729,57 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     d->out_len[1] = s2;
     d->hoff[0] = h1;
     d->hoff[1] = h2;
+    d->routed_ok = P;
     return FR_OK;
+}
+
+// ---- the windows' tally: mode and call order are checked here, the work is fr_dmx_tally.hip's
+static int tally_ready(fr_dmx* d, const char* what) {
+    if (d->key_mode && d->tally) return FR_OK;
+    d->err = std::string(what) + (d->key_mode ? ": no fr_dmx_tally_begin" : ": sheet mode only (fr_dmx_set_sheet)");
+    return FR_ERR_INVALID;
+}
+
+int fr_dmx_tally_begin(fr_dmx* d, uint64_t initial_slots) {
+    if (!d->key_mode) return d->err = "fr_dmx_tally_begin: sheet mode only (fr_dmx_set_sheet)", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    d->routed_ok = 0;
+    return dmx_tally_begin(&d->tally, d->device, d->stream, initial_slots, d->err);
+}
+
+int fr_dmx_tally_file(fr_dmx* d, int64_t file_index) {
+    if (int rc = tally_ready(d, "fr_dmx_tally_file")) return rc;
+    DK(hipSetDevice(d->device));
+    return dmx_tally_file(d->tally, file_index, d->err);
+}
+
+int fr_dmx_tally_window(fr_dmx* d, uint64_t n_pairs, uint64_t first_record) {
+    if (int rc = tally_ready(d, "fr_dmx_tally_window")) return rc;
+    if (n_pairs != d->routed_ok)
+        return d->err = "fr_dmx_tally_window: n_pairs differs from the pairs the last fr_dmx_route routed (or they "
+                        "are counted already)", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    d->routed_ok = 0;
+    return dmx_tally_window(d->tally, d->rkey, n_pairs, first_record, d->err);
+}
+
+int fr_dmx_tally_sizes(fr_dmx* d, uint64_t* n_unique, uint64_t* n_presence) {
+    if (int rc = tally_ready(d, "fr_dmx_tally_sizes")) return rc;
+    DK(hipSetDevice(d->device));
+    return dmx_tally_sizes(d->tally, n_unique, n_presence, d->err);
+}
+
+int fr_dmx_tally_get(fr_dmx* d, uint64_t* keys, uint64_t* counts, uint64_t* first, uint32_t* pres_unique,
+                     uint32_t* pres_file, uint64_t* pres_reads) {
+    if (int rc = tally_ready(d, "fr_dmx_tally_get")) return rc;
+    DK(hipSetDevice(d->device));
+    return dmx_tally_get(d->tally, keys, counts, first, pres_unique, pres_file, pres_reads, d->err);
+}
+
+int fr_dmx_tally_rows_device(fr_dmx* d, void* dev_rows, uint64_t cap) {
+    if (int rc = tally_ready(d, "fr_dmx_tally_rows_device")) return rc;
+    DK(hipSetDevice(d->device));
+    return dmx_tally_rows_device(d->tally, dev_rows, cap, d->err);
 }
 
 // the routed bytes of a mate through its fr_defl: gzip streams (crc32 set) or BGZF member runs

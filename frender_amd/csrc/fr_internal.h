@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
 struct fr_ctx;
@@ -399,5 +400,18 @@ void crc_shift_table(u64 n, u32* T);
 // fr_api.hip, for fr_dmx_set_sheet: the device sheet of ctx and its neighbourhood maps for nsubs (built by the
 // lazy builder when they are not current), complete on the device when the call returns
 int borrow_sheet(::fr_ctx* ctx, int nsubs, int* device, SheetArgs* sh, NbrMap* nm);
+
+// ---- the demux windows' tally (fr_dmx_tally.hip; fr_demux.hip's fr_dmx_tally_* entry points check the mode and
+// the call order and forward here).  Every call returns FR_OK or an FR_ERR_* code with its message in err; the
+// work is queued on the owner's stream.  rec_key: fr_dmx's record keys of the window fr_dmx_route just routed.
+struct DmxTally;
+int dmx_tally_begin(DmxTally** t, int device, hipStream_t stream, u64 initial_slots, std::string& err);
+void dmx_tally_destroy(DmxTally* t);
+int dmx_tally_file(DmxTally* t, i64 file_index, std::string& err);
+int dmx_tally_window(DmxTally* t, const u64* rec_key, u64 n_pairs, u64 first_record, std::string& err);
+int dmx_tally_sizes(DmxTally* t, u64* n_unique, u64* n_presence, std::string& err);
+int dmx_tally_get(DmxTally* t, u64* keys, u64* counts, u64* first, u32* pres_unique, u32* pres_file, u64* pres_reads,
+                  std::string& err);
+int dmx_tally_rows_device(DmxTally* t, void* dev_rows, u64 cap, std::string& err);
 
 }  // namespace fr

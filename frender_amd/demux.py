@@ -9,7 +9,8 @@ errors and gzips each destination's bytes into its writer pair (threads: zlib re
 
 `demux -b SHEET -n N` (not in the reference) needs no results: the GPU classifies every pair's code
 against the sample sheet as `scan -n N` classifies it (fr_dmx_set_sheet, SheetMode below) and the rest is
-the same, so one pass over the inputs writes what scan + demux -r write in two.
+the same, so one pass over the inputs writes what scan + demux -r write in two.  With `--report PATH` the same
+pass also counts every distinct code (fr_dmx_tally_*, Report below) and writes scan's results CSV to PATH.
 """
 from __future__ import annotations
 
@@ -29,7 +30,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import demux_mode, get_indexes, gz_format, input_spec, parse_files, single_index
+from .host import demux_mode, get_indexes, gz_format, input_spec, parse_files, report_args, single_index
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
 # the column order `scan` itself writes (frender.py:482-501, report_analysis)
@@ -479,14 +480,172 @@ class SheetMode:
         return None if which is None else _classification_error(code, which, self.idx1, self.idx2)
 
 
+ORD_SHIFT = 44  # a record's ordinal: (file index + 1) << 44 | its index in the file pair (fr_dmx_tally_file)
+
+
+def merge_report_parts(parts) -> tuple:
+    """The tallies of several ranks as one (`demux --gpus N -b --report`), on the host: parts is a list of
+    (rows, pres, exotic blob) -- int64 rows [n, 3] of (key, count, first), int64 presence triples [m, 3] of
+    (key, file index, reads), and dist._exo_blob's bytes.  Merged by key: count = sum, first = min, presence =
+    union with the reads summed; the exotic tables by string, as a multi-GPU scan merges them.  Returns
+    (rows, pres, (ecodes, ecounts, efirst, epc, epf, epn))."""
+    from .dist import _merge_exotic
+    rows = np.concatenate([np.asarray(p[0], np.int64).reshape(-1, 3) for p in parts])
+    pres = np.concatenate([np.asarray(p[1], np.int64).reshape(-1, 3) for p in parts])
+    keys, inv = np.unique(rows[:, 0], return_inverse=True)
+    inv = inv.reshape(-1)
+    counts = np.zeros(keys.size, np.int64)
+    np.add.at(counts, inv, rows[:, 1])
+    first = np.full(keys.size, np.iinfo(np.int64).max, np.int64)  # ordinals are below 2^63
+    np.minimum.at(first, inv, rows[:, 2])
+    if pres.shape[0]:
+        kf, pinv = np.unique(pres[:, :2], axis=0, return_inverse=True)
+        reads = np.zeros(kf.shape[0], np.int64)
+        np.add.at(reads, pinv.reshape(-1), pres[:, 2])
+        pres = np.concatenate([kf, reads[:, None]], axis=1)
+    return np.stack([keys, counts, first], axis=1), pres, _merge_exotic([p[2] for p in parts])
+
+
+class Report:
+    """`demux -b SHEET -n N --report PATH [-p PREFIX]`: the scan's table, counted in the demux's own pass.  The
+    GPU tallies the fast keys of every routed window (Demux.tally_*: fr_dmx_tally.hip); this object counts the
+    records the host resolved by string (the exotic codes) with the same ordinals, and after the last pair
+    hands the table to the one classifier (scan.process on the sheet context, the rows imported with
+    fr_merge_rows_device) and the one CSV writer (scan.report_analysis), with scan's demux_ok and stdout lines
+    in between (frender.py:636-640, :496)."""
+
+    def __init__(self, path, prefix: str = ""):
+        self.path, self.prefix = str(path), prefix
+        self.exo = {}      # exotic code -> [reads, first ordinal, {file index: reads}]
+        self.records = {}  # file index -> pairs routed
+        self.file = self.pos = 0
+
+    def begin(self, dmx, initial_slots: int = 0):
+        dmx.tally_begin(initial_slots)
+
+    def begin_pair(self, dmx, k: int):
+        dmx.tally_file(k)
+        self.file, self.pos = k, 0
+        self.records[k] = 0
+
+    def window(self, dmx, n_pairs: int, ex, codes):
+        """The window's first n_pairs records are routed: count them.  ex, codes: the records the host resolved
+        and the strings it decoded for that."""
+        dmx.tally_window(n_pairs, self.pos)
+        base = ((self.file + 1) << ORD_SHIFT) | self.pos
+        for r, c in zip(ex.tolist(), codes):
+            e = self.exo.get(c)
+            if e is None:
+                e = self.exo[c] = [0, base + r, {}]
+            e[0] += 1
+            e[1] = min(e[1], base + r)
+            e[2][self.file] = e[2].get(self.file, 0) + 1
+        self.pos += n_pairs
+        self.records[self.file] += n_pairs
+
+    def _exotic(self) -> tuple:
+        codes = list(self.exo)
+        return ([c.encode("utf-8") for c in codes], np.array([self.exo[c][0] for c in codes], dtype=np.uint64),
+                np.array([self.exo[c][1] for c in codes], dtype=np.uint64),
+                np.array([i for i, c in enumerate(codes) for _ in self.exo[c][2]], dtype=np.int64),
+                np.array([f for c in codes for f in sorted(self.exo[c][2])], dtype=np.int64),
+                np.array([self.exo[c][2][f] for c in codes for f in sorted(self.exo[c][2])], dtype=np.uint64))
+
+    def local(self, dmx) -> tuple:
+        """This process's tally once its last pair is done: (rows, pres, exotic tables), merge_report_parts'
+        forms with the exotic tables as arrays."""
+        t = dmx.tally_get()
+        rows = np.stack([t["keys"], t["counts"], t["first"]], axis=1).view(np.int64)
+        pres = np.stack([t["keys"][t["pu"]], t["pf"].astype(np.uint64), t["pn"]], axis=1).view(np.int64)
+        return rows, pres, self._exotic()
+
+    def write(self, part, names, records, sheet, ctx, imported: bool = False):
+        """Classify the table and write the CSV.  part: local()'s or merge_report_parts' tuple; names, records:
+        the pairs' R1 basenames and routed pairs, in pair order; sheet: the SheetMode (its lists as uploaded);
+        ctx: a context no Demux borrows any more -- reset by the caller with the rows merged already when
+        `imported`, else here."""
+        from . import scan
+        rows, pres, exo = part
+        n = int(rows.shape[0])
+        if not imported:
+            ctx.reset()
+            if n:
+                p = ctx.device_alloc(24 * n)
+                try:
+                    ctx.copy_to_device(p, np.ascontiguousarray(rows))
+                    ctx.merge_rows_at(p, n)
+                finally:
+                    ctx.device_free(p)
+        if n:
+            ctx.finalize()
+            keys, counts, first = ctx.unique()  # first-occurrence order
+            assert keys.size == n, "report: the context's table differs from the tally"
+        else:
+            keys = counts = first = np.zeros(0, np.uint64)
+        order = np.argsort(keys, kind="stable")
+        pk = pres[:, 0].view(np.uint64)
+        pu = order[np.searchsorted(keys[order], pk)] if pk.size else np.zeros(0, np.int64)
+        assert not pk.size or bool((keys[pu] == pk).all()), "report: a presence entry's code is not in the table"
+        ecodes, ecounts, efirst, epc, epf, epn = exo
+        t = {"keys": keys, "counts": counts, "first": first, "pu": pu, "pf": pres[:, 1], "pn": pres[:, 2].view(np.uint64),
+             "ecodes": ecodes, "ecounts": ecounts, "efirst": efirst, "epc": epc, "epf": epf, "epn": epn}
+        table = scan.build_table(t, names, records)
+        results = scan.process(1, table, (sheet.idx1, sheet.idx2, sheet.ids), sheet.num_subs, False, ctx=ctx,
+                               single=sheet.single)
+        demux_ok, mismatching = scan.call_barcodes_correctly_distributed(table, results, self.prefix)
+        if mismatching:
+            print("Incorrectly demultiplexed barcodes found! Affected files:")
+            for a in mismatching:
+                print(a)
+        else:
+            print("It appears that all files are already correctly demultiplexed.")
+        scan.report_analysis(table, results, demux_ok, self.path)
+
+    def write_local(self, dmx, sheet, names):
+        """One process, after its last pair: the rows go from the tally to the sheet context on the device."""
+        part = self.local(dmx)
+        ctx, n = sheet.ctx, int(part[0].shape[0])
+        ctx.reset()
+        if n:
+            p = ctx.device_alloc(24 * n)
+            try:
+                dmx.tally_rows_device(p, n)
+                ctx.merge_rows_at(p, n)
+            finally:
+                ctx.device_free(p)
+        dmx.set_table(np.zeros(0, np.uint64), np.zeros(0, np.int32))  # end the borrow: process() uploads the sheet
+        self.write(part, names, [self.records.get(k, 0) for k in range(len(names))], sheet, ctx, imported=True)
+
+    def write_ranks(self, group, wire, part, names, sheet, device: int):
+        """`--gpus N`, no rank failed: every rank's tally (global pair indices in its ordinals and presence
+        triples) to rank 0, which merges them on the host, classifies on a context of its own and writes."""
+        import torch
+
+        from .dist import _exo_blob, gather_bytes, gather_rows
+        rows, pres, exo = part
+        recs = np.array(sorted(self.records.items()), dtype=np.int64).reshape(-1, 2)
+        got = [gather_rows(group, wire, torch.from_numpy(np.ascontiguousarray(a))) for a in (rows, pres, recs)]
+        blobs = gather_bytes(group, wire, _exo_blob(*exo))
+        if group.get_rank() != 0:
+            return
+        merged = merge_report_parts(list(zip(got[0], got[1], blobs)))
+        records = dict(np.concatenate(got[2]).tolist())
+        ctx = _lib.Context(device, chunk_bytes=1 << 20, table_slots=1 << 10)
+        try:
+            self.write(merged, names, [records.get(k, 0) for k in range(len(names))], sheet, ctx)
+        finally:
+            ctx.close()
+
+
 def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of, writers, window, sheet=None,
-                hit=None):
+                hit=None, report=None):
     """One R1/R2 pair in record-aligned windows: the GPU indexes both windows, the complete
     record pairs are routed, and the bytes after the last routed record carry into the next
     window.  Pairing stops when either mate runs out of records (zip, frender.py:777).  The mates
     inflate on the native pool gz (files i1, i2).  sheet (SheetMode): `demux -b`, no results; hit: a set
-    that collects the destinations pairs were routed to."""
-    streams = [text_chunks(read1_file, gz, i1), text_chunks(read2_file, gz, i2)]
+    that collects the destinations pairs were routed to; report (Report, after its begin_pair): `--report`, every
+    routed window is counted."""
+    streams =[text_chunks(read1_file, gz, i1), text_chunks(read2_file, gz, i2)]
     bufs = [[], []]  # each mate's window as a list of decoded blocks (never joined on the host)
     eof = [False, False]
     pending = []  # the previous window's gzip jobs: overlap with this window's inflate and GPU work
@@ -516,6 +675,7 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 window *= 2  # a record longer than the window: widen it
                 continue
             ex = dmx.exotic(n_pairs)
+            codes = []
             if ex.size:  # codes outside the fast alphabet: resolve by string
                 starts, _ = dmx.records(1, ex)
                 codes = [_code_at(bufs, s) for s in starts.tolist()]
@@ -533,6 +693,8 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 if err is not None:
                     raise err
                 raise SystemExit("Unrecognized read type found in supplied frender result file!")
+            if report is not None:  # routed: these n_pairs records are in the output files, and in the table
+                report.window(dmx, n_pairs, ex, codes)
             if hit is not None:
                 hit.update(np.nonzero(b1 + b2)[0].tolist())
             # each mate's bytes for the files and their per-destination sizes, as the writers' family makes them
@@ -639,6 +801,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     dev: a caller's _lib.Demux; ctx: a caller's sheet context for args.b (tests: one with tuning)."""
     t_start = time.perf_counter()
     mode = demux_mode(args)
+    report_path, prefix = report_args(args)
     fmt = gz_format(args)
     single = single_index(args)
     samples = not args.no_samples
@@ -676,6 +839,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     sheet = SheetMode(indexes, args.n, route_of, single) if mode == "b" else None
     lazy = set(range(len(ids))) if sheet is not None and samples else set()  # sample destinations (-b: kept if hit)
     hit = set()
+    report = Report(report_path, prefix) if report_path is not None else None  # --report (with -b: report_args)
 
     table = None
     if mode == "r":
@@ -688,17 +852,23 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     window = int(getattr(args, "window", None) or (512 << 20))  # decoded bytes per mate per GPU pass
     if group is not None:
         return _demux_ranks(group, args, pairs, results, route_of, table, writers, window, level, infix, kind, sheet,
-                            lazy, t_start)
+                            lazy, t_start, report)
     paths = [str(f) for pr in pairs for f in pr]
     try:
         with _session(t_start, paths, kind, len(writers), _device_index(None), sheet, table, dev, ctx,
                       lambda: _close_writers(writers, names, lazy, hit, args.d, infix)) as (dmx, pool, gz):
+            if report is not None:
+                report.begin(dmx)
             for k, (read1_file, read2_file) in enumerate(pairs):
                 print(f"Demultiplexing {read1_file.name}...")
+                if report is not None:
+                    report.begin_pair(dmx, k)
                 _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers,
-                            window, sheet, hit)
+                            window, sheet, hit, report)
             if sheet is not None and samples and not (hit & lazy):
                 print(NO_SAMPLES_WARNING)  # known only now: no pair was demuxable
+            if report is not None:  # every pair is routed: the table is complete
+                report.write_local(dmx, sheet, [str(os.path.basename(r1)) for r1, _ in pairs])
     finally:
         STAGE_TIMES["total"] = time.perf_counter() - t_start
         if getattr(args, "stage_times", False):
@@ -755,7 +925,7 @@ def _mkdir_everywhere(group, path):
 
 
 def _demux_ranks(group, args, pairs, results, route_of, table, names, window, level, infix, kind, sheet, lazy,
-                 t_start):
+                 t_start, report=None):
     import shutil
 
     from .dist import PeerFailed, reduce_min
@@ -763,25 +933,32 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
     parts = os.path.join(args.d, ".frender-parts")
     mine = list(range(rank, len(pairs), world))
     failed, exc = len(pairs), None
+    tally = None  # --report: this rank's table, once its last pair is done
     try:
         # the session opens inside the try: a rank whose pool or device fails still joins the collectives below
         # (-b: this rank's own sheet context: classification is stateless, nothing is exchanged)
         with _session(t_start, [str(f) for k in mine for f in pairs[k]], kind, len(names), _device_index(group),
                       sheet, table) as (dmx, pool, gz):
+            if report is not None:
+                report.begin(dmx)
             for j, k in enumerate(mine):
                 d = os.path.join(parts, str(k))
                 os.makedirs(d, exist_ok=True)
                 writers = [open_files(n, d, infix, level, _BgzfPart if kind is _BgzfDevice else kind) for n in names]
                 hit = set()
                 try:
+                    if report is not None:
+                        report.begin_pair(dmx, k)  # the global pair index: the ordinals are the one-process run's
                     _demux_pair(dmx, pool, gz, 2 * j, 2 * j + 1, pairs[k][0], pairs[k][1], results, route_of, writers,
-                                window, sheet, hit)
+                                window, sheet, hit, report)
                 except (Exception, SystemExit) as e:  # re-raised below if it is the first in pair order
                     failed, exc = k, e
                 finally:
                     _close_writers(writers, names, lazy, hit, d, infix)  # -b: no part for a sample without reads here
                 if exc is not None:
                     break
+            if report is not None and exc is None:
+                tally = report.local(dmx)
     except (Exception, SystemExit) as e:  # before any pair (the device, the table): this rank's first pair
         if exc is None:
             failed, exc = (mine[0] if mine else len(pairs)), e
@@ -818,3 +995,6 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
         if failed == first:
             raise exc
         raise PeerFailed()
+    if report is not None:  # no rank failed: every rank has its table
+        report.write_ranks(group, _wire(group), tally, [str(os.path.basename(r1)) for r1, _ in pairs], sheet,
+                           _device_index(group))

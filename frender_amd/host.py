@@ -158,6 +158,18 @@ def demux_mode(args) -> str:
     return "r" if r is not None else "b"
 
 
+def report_args(args) -> tuple:
+    """--report PATH and -p PREFIX of a demux's arguments: (path or None, prefix).  --report goes with -b only (the
+    one-pass mode counts the codes it classifies; -r has the table already), -p with --report only (scan's
+    prefix for demux_ok).  Called before anything is opened or created, after demux_mode."""
+    path, prefix = getattr(args, "report", None), getattr(args, "p", None)
+    if path is not None and getattr(args, "b", None) is None:
+        raise SystemExit("demux --report: belongs to -b (with -r the result file is the report already)")
+    if prefix is not None and path is None:
+        raise SystemExit("demux -p: belongs to --report (the prefix removed from sample ids for demux_ok, as scan's -p)")
+    return path, prefix or ""
+
+
 def gz_format(args) -> str:
     """--gz-format of a demux's arguments (a namespace without it means gzip), checked against --gz-writer:
     only the GPU writer makes BGZF.  Called before anything is opened or created."""

@@ -401,6 +401,40 @@ int fr_dmx_fetch_deflated(fr_dmx* d, int mate, uint8_t* out, uint64_t len);
  * EOF block is the host's to write. */
 int fr_dmx_deflate_bgzf(fr_dmx* d, int mate, int n_dest, uint64_t* comp_bytes);
 
+/* ---- the demux windows' tally (`demux -b --report`; fr_dmx_tally.hip): the scan's table of every distinct
+ * code, counted over the R2 record keys of the windows a one-pass demux routes, so that one pass over the inputs
+ * gives the output files and the results CSV.  Sheet mode only, off until fr_dmx_tally_begin; the table persists
+ * over all windows and file pairs until the next fr_dmx_tally_begin or fr_dmx_destroy.  Only fast keys are
+ * counted here: a record fr_dmx_exotic reports is the host's to count, by its string.  Every call below returns
+ * FR_ERR_INVALID in table mode or before fr_dmx_tally_begin, and FR_ERR_CAPACITY (never a wrong count) when a
+ * table could not take an entry. */
+/* Start (or clear) the tally.  initial_slots: the HBM table's first size (0: 64 Ki slots; rounded up to a power
+ * of two, at least 64); before a window is counted the table has at least twice as many slots as (distinct keys
+ * so far + the window's pairs), or is rebuilt larger on the device. */
+int fr_dmx_tally_begin(fr_dmx* d, uint64_t initial_slots);
+/* The windows that follow belong to file pair file_index (increasing within a tally, below 2^19): a record's
+ * ordinal is (file_index + 1) << 44 | its index among the pair's records, which orders records as scan's
+ * ordinals do (file order, then position).  Closes the previous pair: its reads per code become presence
+ * entries, the per-file tables scan_file returns (frender.py:171-177) and tally_barcodes keeps (:204-205). */
+int fr_dmx_tally_file(fr_dmx* d, int64_t file_index);
+/* Count the n_pairs records the last fr_dmx_route routed (that call found no negative destination among them;
+ * n_pairs must be its count, and a window is counted once): count += 1 and first = min(ordinal) per code, the
+ * merged table of tally_barcodes (frender.py:199-203).  first_record: the index, within the file pair, of the
+ * window's first record.  Records past n_pairs carry into the next window and are counted there.  Makes no
+ * synchronisation of its own. */
+int fr_dmx_tally_window(fr_dmx* d, uint64_t n_pairs, uint64_t first_record);
+/* Closes the last pair; the sizes of fr_dmx_tally_get's arrays. */
+int fr_dmx_tally_sizes(fr_dmx* d, uint64_t* n_unique, uint64_t* n_presence);
+/* The table as host arrays, in no fixed order: keys (3-bit packed like fr_get_unique's fast keys), counts and
+ * first ordinals per code (barcode_counter["total"], frender.py:199-203), and per (code, file pair) with reads
+ * the code's index in keys, the pair's file index and its reads there (barcode_counter[basename][code],
+ * :204-205; fr_get_presence and fr_get_presence_counts in one). */
+int fr_dmx_tally_get(fr_dmx* d, uint64_t* keys, uint64_t* counts, uint64_t* first, uint32_t* pres_unique,
+                     uint32_t* pres_file, uint64_t* pres_reads);
+/* The same codes as int64 rows [n_unique][3] of (key, count, first) in device memory (cap rows), the form
+ * fr_merge_rows_device takes; complete when the call returns. */
+int fr_dmx_tally_rows_device(fr_dmx* d, void* dev_rows, uint64_t cap);
+
 /* ---- GPU deflate over any byte ranges (fr_deflate.hip; fr_dmx_deflate runs it on the routed bytes).
  * Stream s is bytes [offsets[s], offsets[s + 1]) of the device buffer dev_data (4-byte aligned, 16
  * readable bytes past offsets[n_streams]); every stream becomes one raw deflate stream, no larger than

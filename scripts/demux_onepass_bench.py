@@ -6,13 +6,16 @@ generator), then times whole command lines, each in a process of its own, as a u
 
   two-pass   python -m frender_amd scan -n 1 -b sheet R1...   then   python -m frender_amd demux -r CSV files...
   one-pass   python -m frender_amd demux -b sheet -n 1 files...
+  report     python -m frender_amd demux -b sheet -n 1 --report CSV files...      (with --report-arm only)
 
 The first run of each route is reported as "cold" (this process tree's first use of the GPU, the library and
 the inputs), then --runs alternating runs of both as "warm": medians and min-max.  The decoded content of every
 output file of the two routes is compared (the first runs').  Every demux runs with --stage-times; the
 per-window load+index and route stages of `demux -b`, of this tree's `demux -r` and, with --parent ROOT (a
 built checkout of the parent commit), of the parent's `demux -r` on the same inputs and results file come
-from the same alternating rounds.  Writes one JSON document (--out), stamped with the tree's source hash.
+from the same alternating rounds.  With --report-arm, `demux -b --report` joins the same rounds: it replaces
+scan + demux -r, so that is its comparison, and its CSV is compared with the scan's (the first runs').  Writes one
+JSON document (--out), stamped with the tree's source hash.
 
 Needs a GPU: there is no CPU path to time.
 """
@@ -76,6 +79,8 @@ def main():
     ap.add_argument("--files", type=int, default=16, help="file pairs")
     ap.add_argument("--runs", type=int, default=5, help="alternating warm runs of each route (>= 5)")
     ap.add_argument("--parent", help="root of a built checkout of the parent commit (its demux -r is timed too)")
+    ap.add_argument("--report-arm", action="store_true", help="also time demux -b --report (the results CSV from "
+                                                               "the same pass) in the same rounds")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "demux_sheet_bench.json"))
     ap.add_argument("--workdir", help="where the inputs and outputs go (default: a temporary directory)")
     args = ap.parse_args()
@@ -118,6 +123,14 @@ def main():
                         ROOT)
             return {"total_s": t, "stages": st, "dir": w}
 
+        def report_pass():
+            serial[0] += 1
+            w = os.path.join(d, f"rep_{serial[0]}")
+            os.mkdir(w)
+            t, st = run(["demux", "-b", sheet_csv, "-n", "1", "--report", os.path.join(w, "report.csv"), "-d",
+                         os.path.join(w, "out"), "--stage-times", *allf], w, ROOT)
+            return {"total_s": t, "stages": st, "dir": w, "csv": os.path.join(w, "report.csv")}
+
         def demux_r(root, csv_path):
             serial[0] += 1
             w = os.path.join(d, f"r_{serial[0]}")
@@ -129,14 +142,21 @@ def main():
         cold = {"two_pass": two_pass(), "one_pass": one_pass()}
         da, db = digests(os.path.join(cold["two_pass"]["dir"], "out")), digests(os.path.join(cold["one_pass"]["dir"], "out"))
         equal = da == db
+        report_doc = None
+        if args.report_arm:
+            cold["report"] = report_pass()
+            with open(cold["report"]["csv"], "rb") as f, open(cold["two_pass"]["csv"], "rb") as g:
+                report_doc = {"outputs_equal": digests(os.path.join(cold["report"]["dir"], "out")) == da,
+                              "csv_equals_scan_csv": f.read() == g.read()}
         csv_path = os.path.join(d, "results.csv")
         shutil.copy(cold["two_pass"]["csv"], csv_path)
         out_files = len(da)
         for c in cold.values():
             shutil.rmtree(c["dir"])
-        warm = {"two_pass": [], "one_pass": [], "parent_demux_r": []}
+        warm = {"two_pass": [], "one_pass": [], "report": [], "parent_demux_r": []}
+        arms = (("two_pass", two_pass), ("one_pass", one_pass)) + ((("report", report_pass),) if args.report_arm else ())
         for _ in range(max(args.runs, 5)):
-            for name, fn in (("two_pass", two_pass), ("one_pass", one_pass)):
+            for name, fn in arms:
                 r = fn()
                 shutil.rmtree(r["dir"])
                 warm[name].append(r)
@@ -174,11 +194,22 @@ def main():
             },
             "runs": {k: [strip(r) for r in v] for k, v in warm.items() if v},
         }
+        if report_doc is not None:
+            rep_t = [r["total_s"] for r in warm["report"]]
+            report_doc.update({
+                "what": "demux -b -n 1 --report CSV (output files and results CSV in one pass) against scan -n 1 + "
+                        "demux -r, which it replaces, in the same alternating rounds",
+                "report_total_s": spread(rep_t),
+                "report_over_two_pass": round(statistics.median(rep_t) / statistics.median(two_t), 4),
+                "report_minus_one_pass_s": round(statistics.median(rep_t) - statistics.median(one_t), 4),
+                "M_pairs_per_s": round(n_pairs / statistics.median(rep_t) / 1e6, 4)})
+            doc["report_arm"] = report_doc
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
             f.write("\n")
-        print(json.dumps({k: doc[k] for k in ("tree_hash", "outputs_equal", "warm", "stages_ms_per_window")}))
+        print(json.dumps({k: doc[k] for k in ("tree_hash", "outputs_equal", "warm", "stages_ms_per_window", "report_arm")
+                          if k in doc}))
         if not equal:
             raise SystemExit("the two routes' outputs differ: " +
                              ", ".join(sorted(k for k in set(da) | set(db) if da.get(k) != db.get(k))[:10]))
