@@ -22,6 +22,11 @@ def build_parser() -> argparse.ArgumentParser:
     p = sub.add_parser("scan", help="Scan file(s) or directory and compare to a supplied barcode table")
     p.add_argument("-n", metavar="[int]", type=int, required=True,
                    help="REQUIRED: Number of mismatches allowed between supplied barcodes and fastq file(s)")
+    p.add_argument("--n1", metavar="[int]", type=int, default=None,
+                   help="mismatches allowed in index 1 (default: -n)")
+    p.add_argument("--n2", metavar="[int]", type=int, default=None,
+                   help="mismatches allowed in index 2, and in its reverse complement with -rc (default: -n; not "
+                        "with --single-index)")
     p.add_argument("-rc", action="store_true",
                    help="Scan/demultiplex using reverse complement of index 2 as well as forward sequence")
     p.add_argument("-c", metavar="cores", type=float, default=1,
@@ -71,6 +76,11 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("-n", metavar="[int]", type=int,
                    help="with -b (required there, rejected with -r): number of mismatches allowed between the "
                         "sheet's barcodes and the reads', as scan's -n")
+    d.add_argument("--n1", metavar="[int]", type=int, default=None,
+                   help="with -b: mismatches allowed in index 1 (default: -n), as scan's --n1")
+    d.add_argument("--n2", metavar="[int]", type=int, default=None,
+                   help="with -b: mismatches allowed in index 2 (default: -n; not with --single-index), as scan's "
+                        "--n2")
     d.add_argument("--report", metavar="results_csv",
                    help="with -b: also write the results CSV that `scan -n N -b` writes for the pairs' read 1 files "
                         "(every distinct code with its reads, class, sample and demux_ok), counted in the same "
@@ -111,6 +121,9 @@ def main(argv=None):
         if args.single_index and args.rc:
             from .host import SINGLE_RC_REFUSAL
             parser.error(SINGLE_RC_REFUSAL)
+        if args.single_index and args.n2 is not None:
+            from .host import SINGLE_N2_REFUSAL
+            parser.error(SINGLE_N2_REFUSAL)
         if args.gz_reader == "gpu" and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
             parser.error("--gz-reader gpu is a single-GPU reader: run it without --gpus (multi-GPU scans inflate on "
                          "the host)")
@@ -123,10 +136,11 @@ def main(argv=None):
         frender_scan(args)
         return 0
     if getattr(args, "cmd", None) == "demux":
-        from .host import demux_mode, gz_format, report_args
+        from .host import demux_mode, gz_format, mismatch_limits, report_args
         try:
             demux_mode(args)  # -r or -b with -n, before ranks start (frender_demux checks it too)
             report_args(args)  # --report with -b, -p with --report
+            mismatch_limits(args)  # --n2 with --single-index
         except SystemExit as e:
             parser.error(str(e))
         gz_format(args)  # a bad writer/format pair ends here, before ranks start (frender_demux checks it too)

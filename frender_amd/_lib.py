@@ -16,6 +16,7 @@ import os
 import numpy as np
 
 from . import _runtime
+from .host import limits_of
 
 torch = None
 if _runtime.USE_TORCH:  # one HIP runtime per process (see module doc)
@@ -109,8 +110,11 @@ _SIGS = {
     "fr_exotic_sizes": (C.c_int, [P, u64p, u64p, u64p]),
     "fr_get_exotic_table": (C.c_int, [P, P, P, P, P, P, P]),
     "fr_classify": (C.c_int, [P, C.c_int, C.c_int, P, P, P, P, P, P, P, P, P]),
+    "fr_classify2": (C.c_int, [P, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P, P, P]),
     "fr_rc_counts": (C.c_int, [P, P, P]),
     "fr_classify_cp": (C.c_int, [P, C.c_int, P, P, P, P, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P, P]),
+    "fr_classify_cp2": (C.c_int, [P, C.c_int, P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P,
+                                  P]),
     "fr_export_unique_device": (C.c_int, [P, P, P, P, C.c_uint64]),
     "fr_merge_unique_device": (C.c_int, [P, P, P, P, C.c_uint64]),
     "fr_export_partitioned_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64]),
@@ -149,6 +153,7 @@ _SIGS = {
     "fr_dmx_last_error": (C.c_char_p, [P]),
     "fr_dmx_set_table": (C.c_int, [P, P, P, C.c_uint64]),
     "fr_dmx_set_sheet": (C.c_int, [P, P, C.c_int, P, C.c_int, P]),
+    "fr_dmx_set_sheet2": (C.c_int, [P, P, C.c_int, C.c_int, P, C.c_int, P]),
     "fr_dmx_load": (C.c_int, [P, C.c_int, P, C.c_uint64, u64p]),
     "fr_dmx_load_device": (C.c_int, [P, C.c_int, P, C.c_uint64, u64p]),
     "fr_dmx_records": (C.c_int, [P, C.c_int, P, C.c_uint64, P, P]),
@@ -497,7 +502,7 @@ class Demux:
         self._ck(lib.fr_dmx_set_table(self.h, _ptr(keys), _ptr(vals), keys.size), "fr_dmx_set_table")
         self._sheet_ctx = None
 
-    def set_sheet(self, ctx: "Context", num_subs: int, row_dest, class_dest):
+    def set_sheet(self, ctx: "Context", num_subs, row_dest, class_dest):
         """Sheet mode (fr_dmx_set_sheet): classify every R2 code against ctx's sheet (ctx.set_sheet first) with
         num_subs; row_dest[row] takes a demuxable code, class_dest[class] the others.  ctx stays referenced
         here, and must keep its sheet, until the next set_table / set_sheet / close."""
@@ -505,7 +510,11 @@ class Demux:
         cd = np.ascontiguousarray(class_dest, dtype=np.int32)
         if cd.size != 4:
             raise ValueError("class_dest: one destination per class (4)")
-        self._ck(lib.fr_dmx_set_sheet(self.h, ctx.h, int(num_subs), _ptr(rd), rd.size, _ptr(cd)), "fr_dmx_set_sheet")
+        n1, n2 = (int(v) for v in limits_of(num_subs))
+        if not isinstance(num_subs, (tuple, list)):  # an int: the one-limit entry point; a pair: the two-limit one
+            self._ck(lib.fr_dmx_set_sheet(self.h, ctx.h, n1, _ptr(rd), rd.size, _ptr(cd)), "fr_dmx_set_sheet")
+        else:
+            self._ck(lib.fr_dmx_set_sheet2(self.h, ctx.h, n1, n2, _ptr(rd), rd.size, _ptr(cd)), "fr_dmx_set_sheet2")
         self._sheet_ctx = ctx
 
     def load(self, mate: int, data) -> int:
@@ -942,16 +951,21 @@ class Context:
         return codes, counts, first, pc, pf
 
     # ---- classify -------------------------------------------------------------------
-    def classify(self, num_subs: int, rc: bool, to_host: bool = True):
-        """Classify the finalized table on the GPU; to_host=False leaves the results in HBM."""
+    def classify(self, num_subs, rc: bool, to_host: bool = True):
+        """Classify the finalized table on the GPU; to_host=False leaves the results in HBM.  num_subs: one int
+        for both indexes (fr_classify) or a pair (index 1's limit, index 2's) (fr_classify2)."""
         n = self.U if to_host else 0
         out = {k: (np.empty(n, dtype=np.int16) if to_host else None) for k in ("m1", "m2", "row", "rc_m2", "rc_row")}
         out["cls"] = np.empty(n, dtype=np.uint8) if to_host else None
         out["rc_cls"] = np.empty(n, dtype=np.uint8) if to_host else None
         eu, ew = C.c_int64(), C.c_int32()
-        self._ck(lib.fr_classify(self.h, num_subs, 1 if rc else 0, _ptr(out["m1"]), _ptr(out["m2"]),
-                                 _ptr(out["cls"]), _ptr(out["row"]), _ptr(out["rc_m2"]), _ptr(out["rc_cls"]),
-                                 _ptr(out["rc_row"]), C.byref(eu), C.byref(ew)), "fr_classify")
+        n1, n2 = (int(v) for v in limits_of(num_subs))
+        tail = (1 if rc else 0, _ptr(out["m1"]), _ptr(out["m2"]), _ptr(out["cls"]), _ptr(out["row"]),
+                _ptr(out["rc_m2"]), _ptr(out["rc_cls"]), _ptr(out["rc_row"]), C.byref(eu), C.byref(ew))
+        if not isinstance(num_subs, (tuple, list)):
+            self._ck(lib.fr_classify(self.h, n1, *tail), "fr_classify")
+        else:
+            self._ck(lib.fr_classify2(self.h, n1, n2, *tail), "fr_classify2")
         out["err_unique"], out["err_which"] = eu.value, ew.value
         return out
 
@@ -961,7 +975,7 @@ class Context:
         self._ck(lib.fr_rc_counts(self.h, _ptr(f), _ptr(r)), "fr_rc_counts")
         return f[:self.n_names], r[:self.n_names]
 
-    def classify_cp(self, q1: list, q2: list, num_subs: int, rc: bool):
+    def classify_cp(self, q1: list, q2: list, num_subs, rc: bool):
         n = len(q1)
         stride = self.cp_stride
         a1 = np.zeros((n, stride), dtype=np.uint32)
@@ -975,10 +989,14 @@ class Context:
         out["cls"] = np.empty(n, dtype=np.uint8)
         out["rc_cls"] = np.empty(n, dtype=np.uint8)
         out["err"] = np.zeros(n, dtype=np.int32)
-        self._ck(lib.fr_classify_cp(self.h, n, _ptr(a1), _ptr(l1), _ptr(a2), _ptr(l2), stride, num_subs,
-                                    1 if rc else 0, _ptr(out["m1"]), _ptr(out["m2"]), _ptr(out["cls"]),
-                                    _ptr(out["row"]), _ptr(out["rc_m2"]), _ptr(out["rc_cls"]), _ptr(out["rc_row"]),
-                                    _ptr(out["err"])), "fr_classify_cp")
+        n1, n2 = (int(v) for v in limits_of(num_subs))
+        head = (self.h, n, _ptr(a1), _ptr(l1), _ptr(a2), _ptr(l2), stride)
+        tail = (1 if rc else 0, _ptr(out["m1"]), _ptr(out["m2"]), _ptr(out["cls"]), _ptr(out["row"]),
+                _ptr(out["rc_m2"]), _ptr(out["rc_cls"]), _ptr(out["rc_row"]), _ptr(out["err"]))
+        if not isinstance(num_subs, (tuple, list)):
+            self._ck(lib.fr_classify_cp(*head, n1, *tail), "fr_classify_cp")
+        else:
+            self._ck(lib.fr_classify_cp2(*head, n1, n2, *tail), "fr_classify_cp2")
         return out
 
     # ---- device memory / synthetic data / timing --------------------------------------
@@ -1011,8 +1029,8 @@ class Context:
         return t
 
     def diag(self) -> dict:
-        v = np.zeros(26, dtype=np.uint64)
-        self._ck(lib.fr_get_diag(self.h, _ptr(v), 26), "fr_get_diag")
+        v = np.zeros(27, dtype=np.uint64)
+        self._ck(lib.fr_get_diag(self.h, _ptr(v), 27), "fr_get_diag")
         d = dict(zip(("spin_max", "spin_total", "keys", "overflow", "presence", "exotic", "grid", "slots"),
                      v[:8].tolist()))
         d["spec_replays"] = int(v[16])
@@ -1027,6 +1045,7 @@ class Context:
         # own between the kernels, and a steady one-file device-feed step queues none
         d["stream_fills"] = int(v[24])
         d["stream_copies"] = int(v[25])
+        d["nbr_on"] = int(v[26])  # the neighbourhood maps were on for the last classify / sheet borrow
         if v[8:16].any():  # FR_TIMING build / FR_ABLATE=64: per-phase cycles or commit counts
             names = ("guess", "walk0", "wait0", "resolve", "walk1", "commit", "kernel", "chunks")
             d["stamps"] = dict(zip(names, v[8:].tolist()))

@@ -192,11 +192,11 @@ struct fr_ctx {
     int32_t* d_canon = nullptr;  // per list (idx1, idx2, rc(idx2)): the first row holding the row's value
     u64 sheet_ver = 0;           // bumped on every upload of a different sheet
 
-    // classify neighbourhood maps (fr_internal.h NbrMap) of sheet version nbr_ver and nbr_nsubs
+    // classify neighbourhood maps (fr_internal.h NbrMap) of sheet version nbr_ver and radii nbr_nsubs1, nbr_nsubs2
     u8* d_nbr = nullptr;
     u64 nbr_cap = 0;
     u64 nbr_ver = ~0ull;
-    int nbr_nsubs = -1, nbr_rc = 0;
+    int nbr_nsubs1 = -1, nbr_nsubs2 = -1, nbr_rc = 0;
     NbrMap nbr{};
     bool nbr_enabled = true;  // FR_NBR=0: every code takes the row scan (A/B and tests)
 
@@ -866,7 +866,8 @@ int fr_get_diag(fr_ctx* ctx, uint64_t* out, int n) {
                           s.stamp[4],  s.stamp[5],  s.stamp[6], s.stamp[7], ctx->spec_replays, ctx->exo_replays,
                           s.heavy[ctx->par] ? ctx->chunk_tiles_heavy : ctx->chunk_tiles,  // the next ramped launch's
                           s.heavy_launches, ctx->big_rollbacks, ctx->feed_fold_max, ctx->feed_fold_over, ctx->feed_step,
-                          ctx->n_fills, ctx->n_copies};  // (new entries go at the end: the indices are the ABI)
+                          ctx->n_fills, ctx->n_copies,
+                          (uint64_t)(ctx->nbr.on ? 1 : 0)};  // (new entries go at the end: the indices are the ABI)
     for (int i = 0; i < n && i < (int)(sizeof(v) / sizeof(v[0])); ++i) out[i] = v[i];
     return FR_OK;
 }
@@ -1660,19 +1661,24 @@ static int ensure_class_scratch(fr_ctx* ctx, u64 n) {
     return FR_OK;
 }
 
-// the classify neighbourhood maps of the current sheet and nsubs (stream-ordered, rebuilt only when
-// the sheet, nsubs or the rc need changed); nbr.on = 0 when the sheet does not suit them (mixed or
-// > 21-symbol lengths, or more than NBR_MAX codes per list) or FR_NBR=0
-static int ensure_nbr(fr_ctx* ctx, const SheetArgs& sh, int nsubs, int rc) {
+// the classify neighbourhood maps of the current sheet and radii: the idx1 list at nsubs1, the idx2 and rc(idx2)
+// lists at nsubs2 (stream-ordered, rebuilt only when the sheet, a radius or the rc need changed); nbr.on = 0 when
+// the sheet does not suit them (mixed or > 21-symbol lengths, a negative radius, or more than NBR_MAX codes in a
+// list at its own radius: all three maps or none) or FR_NBR=0
+static int ensure_nbr(fr_ctx* ctx, const SheetArgs& sh, int nsubs1, int nsubs2, int rc) {
     constexpr u64 NBR_MAX = 1ull << 21;
-    if (ctx->nbr_ver == ctx->sheet_ver && ctx->nbr_nsubs == nsubs && (ctx->nbr_rc || !rc)) return FR_OK;
+    if (ctx->nbr_ver == ctx->sheet_ver && ctx->nbr_nsubs1 == nsubs1 && ctx->nbr_nsubs2 == nsubs2 &&
+        (ctx->nbr_rc || !rc))
+        return FR_OK;
     ctx->nbr.on = 0;
     ctx->nbr_ver = ctx->sheet_ver;
-    ctx->nbr_nsubs = nsubs;
+    ctx->nbr_nsubs1 = nsubs1;
+    ctx->nbr_nsubs2 = nsubs2;
     ctx->nbr_rc = rc;
-    if (!ctx->nbr_enabled || sh.S <= 0 || nsubs < 0 || sh.L1u < 0 || sh.L1u > 21 || sh.L2u < 0 || sh.L2u > 21)
+    if (!ctx->nbr_enabled || sh.S <= 0 || nsubs1 < 0 || nsubs2 < 0 || sh.L1u < 0 || sh.L1u > 21 || sh.L2u < 0 ||
+        sh.L2u > 21)
         return FR_OK;
-    const u64 c1 = (u64)sh.S * nbr_codes_per_row(sh.L1u, nsubs), c2 = (u64)sh.S * nbr_codes_per_row(sh.L2u, nsubs);
+    const u64 c1 = (u64)sh.S * nbr_codes_per_row(sh.L1u, nsubs1), c2 = (u64)sh.S * nbr_codes_per_row(sh.L2u, nsubs2);
     if (c1 > NBR_MAX || c2 > NBR_MAX) return FR_OK;
     const u64 n1 = std::max<u64>(pow2_at_least(2 * c1), 1024), n2 = std::max<u64>(pow2_at_least(2 * c2), 1024);
     const u64 np = std::max<u64>(pow2_at_least(2 * (u64)sh.S), 64);
@@ -1695,16 +1701,23 @@ static int ensure_nbr(fr_ctx* ctx, const SheetArgs& sh, int nsubs, int rc) {
     m.mmask[1] = m.mmask[2] = (u32)(n2 - 1);
     m.pmask[0] = m.pmask[1] = (u32)(np - 1);
     CK(fill_async(ctx, ctx->d_nbr, 0, bytes));
-    CK(launch_nbr_build(sh, ctx->d_canon, nsubs, rc, m, ctx->stream));
+    CK(launch_nbr_build(sh, ctx->d_canon, nsubs1, nsubs2, rc, m, ctx->stream));
     m.on = 1;
     return FR_OK;
 }
 
 int fr_classify(fr_ctx* ctx, int num_subs, int rc_mode, int16_t* m1, int16_t* m2, uint8_t* cls, int16_t* row,
                 int16_t* rc_m2, uint8_t* rc_cls, int16_t* rc_row, int64_t* err_unique, int32_t* err_which) {
-    if (ctx->S < 0) return fail(ctx, FR_ERR_INVALID, "fr_classify: no sheet");
+    return fr_classify2(ctx, num_subs, num_subs, rc_mode, m1, m2, cls, row, rc_m2, rc_cls, rc_row, err_unique,
+                        err_which);
+}
+
+int fr_classify2(fr_ctx* ctx, int num_subs1, int num_subs2, int rc_mode, int16_t* m1, int16_t* m2, uint8_t* cls,
+                 int16_t* row, int16_t* rc_m2, uint8_t* rc_cls, int16_t* rc_row, int64_t* err_unique,
+                 int32_t* err_which) {
+    if (ctx->S < 0) return fail(ctx, FR_ERR_INVALID, "fr_classify[2]: no sheet");
     if (ctx->sheet_single && rc_mode)
-        return fail(ctx, FR_ERR_INVALID, "fr_classify: no rc_mode on a single-index sheet (there is no index 2)");
+        return fail(ctx, FR_ERR_INVALID, "fr_classify[2]: no rc_mode on a single-index sheet (there is no index 2)");
     const u64 n = ctx->U;
     int rc = ensure_class_scratch(ctx, n);
     if (rc) return rc;
@@ -1715,13 +1728,13 @@ int fr_classify(fr_ctx* ctx, int num_subs, int rc_mode, int16_t* m1, int16_t* m2
     u64* next = ctx->d_errf + (u64)(ctx->errf_cur ^ 1) * ctx->errf_words;
     SheetArgs sh{ctx->S, ctx->n_names, ctx->L1u, ctx->L2u, ctx->d_i1, ctx->d_i2, ctx->d_i2rc, ctx->d_name,
                  ctx->sheet_single};
-    if ((rc = ensure_nbr(ctx, sh, num_subs, rc_mode ? 1 : 0))) return rc;
+    if ((rc = ensure_nbr(ctx, sh, num_subs1, num_subs2, rc_mode ? 1 : 0))) return rc;
     ClassOut o{ctx->d_m1, ctx->d_m2, ctx->d_cls, ctx->d_row, ctx->d_rm2, ctx->d_rcls, ctx->d_rrow,
                blk + 1, blk + 1 + ctx->rc_names_cap, blk, ctx->d_errw};
     const bool timed = ctx->timing;
     if (timed) CK(hipEventRecord(e0, ctx->stream));
     ctx->h_mir->err_flag = 0;
-    CK(launch_classify(ctx->d_keys_s, ctx->d_counts_s, n, sh, num_subs, rc_mode ? 1 : 0, o, ctx->nbr, next,
+    CK(launch_classify(ctx->d_keys_s, ctx->d_counts_s, n, sh, num_subs1, num_subs2, rc_mode ? 1 : 0, o, ctx->nbr, next,
                        (u32)ctx->errf_words, &ctx->d_mir->err_flag, ctx->stream));
     ctx->errf_cur ^= 1;
     ctx->d_rcf = o.rc_f;  // fr_rc_counts reads this call's sums until the next one
@@ -1780,12 +1793,20 @@ int fr_classify_cp(fr_ctx* ctx, int n, const uint32_t* q1, const int32_t* q1len,
                    const int32_t* q2len, int cp_stride, int num_subs, int rc_mode, int16_t* m1, int16_t* m2,
                    uint8_t* cls, int16_t* row, int16_t* rc_m2, uint8_t* rc_cls, int16_t* rc_row,
                    int32_t* err_which) {
+    return fr_classify_cp2(ctx, n, q1, q1len, q2, q2len, cp_stride, num_subs, num_subs, rc_mode, m1, m2, cls, row,
+                           rc_m2, rc_cls, rc_row, err_which);
+}
+
+int fr_classify_cp2(fr_ctx* ctx, int n, const uint32_t* q1, const int32_t* q1len, const uint32_t* q2,
+                    const int32_t* q2len, int cp_stride, int num_subs1, int num_subs2, int rc_mode, int16_t* m1,
+                    int16_t* m2, uint8_t* cls, int16_t* row, int16_t* rc_m2, uint8_t* rc_cls, int16_t* rc_row,
+                    int32_t* err_which) {
     if (int src = settle_finalize(ctx)) return src;
     if (n <= 0) return FR_OK;
     if (ctx->sheet_single && rc_mode)
-        return fail(ctx, FR_ERR_INVALID, "fr_classify_cp: no rc_mode on a single-index sheet (there is no index 2)");
+        return fail(ctx, FR_ERR_INVALID, "fr_classify_cp[2]: no rc_mode on a single-index sheet (there is no index 2)");
     if (ctx->S > 0 && (!ctx->d_cp1 || cp_stride != ctx->cp_stride))
-        return fail(ctx, FR_ERR_INVALID, "fr_classify_cp: sheet code points missing or stride mismatch");
+        return fail(ctx, FR_ERR_INVALID, "fr_classify_cp[2]: sheet code points missing or stride mismatch");
     u32 *dq1, *dq2;
     int32_t *dl1, *dl2;
     int16_t *o_m1, *o_m2, *o_row, *o_rm2, *o_rrow;
@@ -1810,8 +1831,8 @@ int fr_classify_cp(fr_ctx* ctx, int n, const uint32_t* q1, const int32_t* q1len,
     CK(hipMemcpy(dl2, q2len, n * 4, hipMemcpyHostToDevice));
     ClassOut o{o_m1, o_m2, o_cls, o_row, o_rm2, o_rcls, o_rrow, nullptr, nullptr, nullptr, o_err};
     CK(launch_classify_cp(n, dq1, dl1, dq2, dl2, cp_stride, ctx->S > 0 ? ctx->S : 0, ctx->d_cp1, ctx->d_cpl1,
-                          ctx->d_cp2, ctx->d_cpl2, ctx->d_cp2rc, ctx->d_name, num_subs, rc_mode ? 1 : 0, o,
-                          ctx->stream));
+                          ctx->d_cp2, ctx->d_cpl2, ctx->d_cp2rc, ctx->d_name, num_subs1, num_subs2, rc_mode ? 1 : 0,
+                          o, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     CK(hipMemcpy(m1, o_m1, n * 2, hipMemcpyDeviceToHost));
     CK(hipMemcpy(m2, o_m2, n * 2, hipMemcpyDeviceToHost));
@@ -1931,12 +1952,12 @@ int fr_synth_device(fr_ctx* ctx, uint8_t* dev_out, uint64_t r0, uint64_t n, int 
 }  // extern "C"
 
 namespace fr {
-int borrow_sheet(fr_ctx* ctx, int nsubs, int* device, SheetArgs* sh, NbrMap* nm) {
-    if (ctx->S < 0) return fail(ctx, FR_ERR_INVALID, "fr_dmx_set_sheet: no sheet");
+int borrow_sheet(fr_ctx* ctx, int nsubs1, int nsubs2, int* device, SheetArgs* sh, NbrMap* nm) {
+    if (ctx->S < 0) return fail(ctx, FR_ERR_INVALID, "fr_dmx_set_sheet[2]: no sheet");
     CK(hipSetDevice(ctx->device));
     *sh = SheetArgs{ctx->S, ctx->n_names, ctx->L1u, ctx->L2u, ctx->d_i1, ctx->d_i2, ctx->d_i2rc, ctx->d_name,
                     ctx->sheet_single};
-    if (int rc = ensure_nbr(ctx, *sh, nsubs, 0)) return rc;
+    if (int rc = ensure_nbr(ctx, *sh, nsubs1, nsubs2, 0)) return rc;
     CK(hipStreamSynchronize(ctx->stream));  // the sheet upload and the map build: the demux reads them on its own stream
     *nm = ctx->nbr;
     *device = ctx->device;

@@ -76,14 +76,14 @@ __device__ __forceinline__ PairClass class_rule(int m1, int m2, int rm2, int bot
 // (a code matches one or two rows of a well-separated sheet: the wave skips ~2/3 of the updates).
 template <typename W, bool RC>
 __device__ __forceinline__ PairClass class_pair_s(W q1, W q2, const u64* __restrict__ s1, const u64* __restrict__ s2,
-                                                  const u64* __restrict__ s2rc, int S, int nsubs) {
+                                                  const u64* __restrict__ s2rc, int S, int nsubs1, int nsubs2) {
     int m1 = -1, m2 = -1, rm2 = -1;
     int both = 0, r = -1, rboth = 0, rr = -1;
 #pragma unroll 8
     for (int i = 0; i < S; ++i) {
-        const bool a = mism_w<W>(q1, (W)s1[i]) <= nsubs;
-        const bool b = mism_w<W>(q2, (W)s2[i]) <= nsubs;
-        const bool c = RC && mism_w<W>(q2, (W)s2rc[i]) <= nsubs;
+        const bool a = mism_w<W>(q1, (W)s1[i]) <= nsubs1;
+        const bool b = mism_w<W>(q2, (W)s2[i]) <= nsubs2;
+        const bool c = RC && mism_w<W>(q2, (W)s2rc[i]) <= nsubs2;
         if (a || b || c) {
             m1 = (a && m1 < 0) ? i : m1;
             m2 = (b && m2 < 0) ? i : m2;
@@ -171,11 +171,12 @@ __global__ void nbr_pair_kernel(const int32_t* __restrict__ canon, int S, int rc
     }
 }
 
-hipError_t launch_nbr_build(const SheetArgs& sh, const int32_t* canon, int nsubs, int rc, const NbrMap& nm,
-                            hipStream_t s) {
+hipError_t launch_nbr_build(const SheetArgs& sh, const int32_t* canon, int nsubs1, int nsubs2, int rc,
+                            const NbrMap& nm, hipStream_t s) {
     const u64* vals[3] = {sh.i1, sh.i2, sh.i2rc};
     const int len[3] = {sh.L1u, sh.L2u, sh.L2u};
     for (int l = 0; l < (rc ? 3 : 2); ++l) {
+        const int nsubs = l == 0 ? nsubs1 : nsubs2;  // the idx1 list at its radius, idx2 and rc(idx2) at theirs
         const u64 T = nbr_codes_per_row(len[l], nsubs);
         const u64 n = (u64)sh.S * T;
         hipLaunchKernelGGL(nbr_insert_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, s, vals[l], canon + l * sh.S,
@@ -318,19 +319,21 @@ __device__ __forceinline__ int length_error(const SheetArgs& sh, int n1, int n2)
 // One split code against the sheet: the maps when they are on, the exact row scan when they are off or a map
 // answers -2 (the code lies near several distinct sheet values).  Without RC a3 stays -1.
 template <typename W, bool RC>
-__device__ __forceinline__ PairClass class_code(const SheetArgs& sh, const NbrMap& nm, u64 q1, u64 q2, int nsubs) {
+__device__ __forceinline__ PairClass class_code(const SheetArgs& sh, const NbrMap& nm, u64 q1, u64 q2, int nsubs1,
+                                                int nsubs2) {
     int a1 = -2, a2 = -2, a3 = -1;
     if (nm.on) nbr_find3(nm, q1, q2, RC, a1, a2, a3);
     if (a1 != -2 && a2 != -2 && a3 != -2) return class_pair_nbr(nm, a1, a2, a3);
-    return class_pair_s<W, RC>((W)q1, (W)q2, sh.i1, sh.i2, sh.i2rc, sh.S, nsubs);
+    return class_pair_s<W, RC>((W)q1, (W)q2, sh.i1, sh.i2, sh.i2rc, sh.S, nsubs1, nsubs2);
 }
 
 // One lane per unique code; W is u32 when every sheet entry has <= 10 symbols, else u64.  The per-name rc
 // sums live in dynamic LDS when they fit (names_in_lds), else they go to the global atomics.
 template <typename W>
 __global__ __launch_bounds__(CLS_WG) void classify_kernel(const u64* keys, const u64* counts, u64 n, SheetArgs sh,
-                                                          int nsubs, int rc, ClassOut o, NbrMap nm, int names_in_lds,
-                                                          u64* zero_next, u32 zero_n, u64* err_flag) {
+                                                          int nsubs1, int nsubs2, int rc, ClassOut o, NbrMap nm,
+                                                          int names_in_lds, u64* zero_next, u32 zero_n,
+                                                          u64* err_flag) {
     extern __shared__ __attribute__((aligned(16))) u8 cls_lds[];
     // the error word + rc sums of the next fr_classify (the other of two alternating blocks): zeroed here,
     // so no call issues a memset dispatch for its own
@@ -354,7 +357,8 @@ __global__ __launch_bounds__(CLS_WG) void classify_kernel(const u64* keys, const
         const int err = plus ? length_error(sh, n1, n2) : 3;
         PairClass c = {-1, -1, CLS_UNDET, -1, -1, CLS_UNDET, -1};
         if (!err) {
-            c = rc ? class_code<W, true>(sh, nm, q1, q2, nsubs) : class_code<W, false>(sh, nm, q1, q2, nsubs);
+            c = rc ? class_code<W, true>(sh, nm, q1, q2, nsubs1, nsubs2)
+                   : class_code<W, false>(sh, nm, q1, q2, nsubs1, nsubs2);
             // both calls demuxable to different sample NAMES -> ambiguous (frender.py:336-349)
             if (rc && c.cls == CLS_DEMUX && c.rcls == CLS_DEMUX && sh.name[c.row] != sh.name[c.rrow]) {
                 c.cls = CLS_AMBIG;
@@ -409,19 +413,19 @@ static bool sheet_is_narrow(const SheetArgs& sh) {
     return sh.S > 0 && sh.L1u >= 0 && sh.L1u <= 10 && sh.L2u >= 0 && sh.L2u <= 10;
 }
 
-hipError_t launch_classify(const u64* keys, const u64* counts, u64 n, SheetArgs sh, int nsubs, int rc, ClassOut o,
-                           const NbrMap& nm, u64* zero_next, u32 zero_n, u64* err_flag, hipStream_t s) {
+hipError_t launch_classify(const u64* keys, const u64* counts, u64 n, SheetArgs sh, int nsubs1, int nsubs2, int rc,
+                           ClassOut o, const NbrMap& nm, u64* zero_next, u32 zero_n, u64* err_flag, hipStream_t s) {
     // (no codes: one workgroup still zeroes the next call's block)
     const size_t names_bytes = rc ? 2ull * 8 * sh.n_names : 0;
     const int names_in_lds = (rc && names_bytes <= CLS_LDS_BYTES / 2) ? 1 : 0;
     const size_t lds = (names_in_lds ? names_bytes : 0) + 16;
     const u64 grid = std::max<u64>(1, std::min<u64>((n + CLS_WG - 1) / CLS_WG, 2048));
     if (sheet_is_narrow(sh))
-        hipLaunchKernelGGL(classify_kernel<u32>, dim3((u32)grid), dim3(CLS_WG), lds, s, keys, counts, n, sh, nsubs, rc,
-                           o, nm, names_in_lds, zero_next, zero_n, err_flag);
+        hipLaunchKernelGGL(classify_kernel<u32>, dim3((u32)grid), dim3(CLS_WG), lds, s, keys, counts, n, sh, nsubs1,
+                           nsubs2, rc, o, nm, names_in_lds, zero_next, zero_n, err_flag);
     else
-        hipLaunchKernelGGL(classify_kernel<u64>, dim3((u32)grid), dim3(CLS_WG), lds, s, keys, counts, n, sh, nsubs, rc,
-                           o, nm, names_in_lds, zero_next, zero_n, err_flag);
+        hipLaunchKernelGGL(classify_kernel<u64>, dim3((u32)grid), dim3(CLS_WG), lds, s, keys, counts, n, sh, nsubs1,
+                           nsubs2, rc, o, nm, names_in_lds, zero_next, zero_n, err_flag);
     return hipGetLastError();
 }
 
@@ -432,7 +436,7 @@ hipError_t launch_classify(const u64* keys, const u64* counts, u64 n, SheetArgs 
 // ------------------------------------------------------------------------------------
 template <typename W>
 __global__ __launch_bounds__(CLS_WG) void dmx_class_kernel(const u64* __restrict__ rec_key, int32_t* rec_dest, u64 n,
-                                                           SheetArgs sh, int nsubs, NbrMap nm,
+                                                           SheetArgs sh, int nsubs1, int nsubs2, NbrMap nm,
                                                            const int32_t* __restrict__ row_dest, DmxClassDest cd) {
     for (u64 u = blockIdx.x * (u64)CLS_WG + threadIdx.x; u < n; u += (u64)gridDim.x * CLS_WG) {
         if (rec_dest[u] != DMX_PENDING) continue;  // exotic: the host resolves it
@@ -444,7 +448,7 @@ __global__ __launch_bounds__(CLS_WG) void dmx_class_kernel(const u64* __restrict
         } else if (const int err = length_error(sh, n1, n2)) {
             d = err == 1 ? FR_DMX_LEN1 : FR_DMX_LEN2;
         } else {
-            const PairClass c = class_code<W, false>(sh, nm, q1, q2, nsubs);
+            const PairClass c = class_code<W, false>(sh, nm, q1, q2, nsubs1, nsubs2);
             d = c.cls == CLS_DEMUX   ? row_dest[c.row]
                 : c.cls == CLS_HOP   ? cd.v[CLS_HOP]
                 : c.cls == CLS_AMBIG ? cd.v[CLS_AMBIG]
@@ -454,22 +458,22 @@ __global__ __launch_bounds__(CLS_WG) void dmx_class_kernel(const u64* __restrict
     }
 }
 
-hipError_t launch_dmx_classify(const u64* rec_key, int32_t* rec_dest, u64 n, SheetArgs sh, int nsubs,
+hipError_t launch_dmx_classify(const u64* rec_key, int32_t* rec_dest, u64 n, SheetArgs sh, int nsubs1, int nsubs2,
                                const NbrMap& nm, const int32_t* row_dest, DmxClassDest cd, hipStream_t s) {
     if (!n) return hipSuccess;
     const u64 grid = std::max<u64>(1, std::min<u64>((n + CLS_WG - 1) / CLS_WG, 2048));
     if (sheet_is_narrow(sh))
-        hipLaunchKernelGGL(dmx_class_kernel<u32>, dim3((u32)grid), dim3(CLS_WG), 0, s, rec_key, rec_dest, n, sh, nsubs,
-                           nm, row_dest, cd);
+        hipLaunchKernelGGL(dmx_class_kernel<u32>, dim3((u32)grid), dim3(CLS_WG), 0, s, rec_key, rec_dest, n, sh, nsubs1,
+                           nsubs2, nm, row_dest, cd);
     else
-        hipLaunchKernelGGL(dmx_class_kernel<u64>, dim3((u32)grid), dim3(CLS_WG), 0, s, rec_key, rec_dest, n, sh, nsubs,
-                           nm, row_dest, cd);
+        hipLaunchKernelGGL(dmx_class_kernel<u64>, dim3((u32)grid), dim3(CLS_WG), 0, s, rec_key, rec_dest, n, sh, nsubs1,
+                           nsubs2, nm, row_dest, cd);
     return hipGetLastError();
 }
 
 // generic classifier over case-folded code points (codes outside the fast alphabet): class_pair_s on strings
 __device__ PairClass class_pair_cp(const u32* q1, int n1, const u32* q2, int n2, const u32* s1, const u32* s2,
-                                   const u32* s2rc, int stride, int S, int nsubs, bool rc) {
+                                   const u32* s2rc, int stride, int S, int nsubs1, int nsubs2, bool rc) {
     int m1 = -1, m2 = -1, rm2 = -1;
     int both = 0, r = -1, rboth = 0, rr = -1;
     for (int i = 0; i < S; ++i) {
@@ -477,7 +481,7 @@ __device__ PairClass class_pair_cp(const u32* q1, int n1, const u32* q2, int n2,
         for (int k = 0; k < n1; ++k) d1 += q1[k] != s1[(u64)i * stride + k];
         for (int k = 0; k < n2; ++k) d2 += q2[k] != s2[(u64)i * stride + k];
         for (int k = 0; rc && k < n2; ++k) d3 += q2[k] != s2rc[(u64)i * stride + k];
-        const bool a = d1 <= nsubs, b = d2 <= nsubs, c = rc && d3 <= nsubs;
+        const bool a = d1 <= nsubs1, b = d2 <= nsubs2, c = rc && d3 <= nsubs2;
         m1 = (a && m1 < 0) ? i : m1;
         m2 = (b && m2 < 0) ? i : m2;
         r = (a && b && both == 0) ? i : r;
@@ -491,8 +495,8 @@ __device__ PairClass class_pair_cp(const u32* q1, int n1, const u32* q2, int n2,
 
 __global__ void classify_cp_kernel(int n, const u32* q1, const int32_t* q1len, const u32* q2, const int32_t* q2len,
                                    int stride, int S, const u32* s1, const int32_t* s1len, const u32* s2,
-                                   const int32_t* s2len, const u32* s2rc, const int32_t* name, int nsubs, int rc,
-                                   ClassOut o) {
+                                   const int32_t* s2len, const u32* s2rc, const int32_t* name, int nsubs1, int nsubs2,
+                                   int rc, ClassOut o) {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= n) return;
     const int n1 = q1len[u], n2 = q2len[u];
@@ -503,7 +507,8 @@ __global__ void classify_cp_kernel(int n, const u32* q1, const int32_t* q1len, c
         if (s2len[i] != n2) err = 2;
     PairClass c = {-1, -1, CLS_UNDET, -1, -1, CLS_UNDET, -1};
     if (!err) {
-        c = class_pair_cp(q1 + (u64)u * stride, n1, q2 + (u64)u * stride, n2, s1, s2, s2rc, stride, S, nsubs, rc != 0);
+        c = class_pair_cp(q1 + (u64)u * stride, n1, q2 + (u64)u * stride, n2, s1, s2, s2rc, stride, S, nsubs1, nsubs2,
+                          rc != 0);
         if (rc && c.cls == CLS_DEMUX && c.rcls == CLS_DEMUX && name[c.row] != name[c.rrow]) {
             c.cls = c.rcls = CLS_AMBIG;
             c.row = c.rrow = -1;
@@ -523,11 +528,11 @@ __global__ void classify_cp_kernel(int n, const u32* q1, const int32_t* q1len, c
 
 hipError_t launch_classify_cp(int n, const u32* q1, const int32_t* q1len, const u32* q2, const int32_t* q2len,
                               int stride, int S, const u32* s1, const int32_t* s1len, const u32* s2,
-                              const int32_t* s2len, const u32* s2rc, const int32_t* name, int nsubs, int rc,
-                              ClassOut o, hipStream_t s) {
+                              const int32_t* s2len, const u32* s2rc, const int32_t* name, int nsubs1, int nsubs2,
+                              int rc, ClassOut o, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(classify_cp_kernel, dim3((n + 127) / 128), dim3(128), 0, s, n, q1, q1len, q2, q2len, stride,
-                       S, s1, s1len, s2, s2len, s2rc, name, nsubs, rc, o);
+                       S, s1, s1len, s2, s2len, s2rc, name, nsubs1, nsubs2, rc, o);
     return hipGetLastError();
 }
 

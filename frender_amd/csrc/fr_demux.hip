@@ -369,7 +369,7 @@ struct fr_dmx {
     bool key_mode = false;
     SheetArgs sheet{};
     NbrMap nbr{};
-    int nsubs = 0;
+    int nsubs1 = 0, nsubs2 = 0;
     int32_t* row_dest = nullptr;
     DmxClassDest class_dest{};
     u64* rkey = nullptr;
@@ -487,17 +487,22 @@ int fr_dmx_set_table(fr_dmx* d, const uint64_t* keys, const int32_t* vals, uint6
 
 int fr_dmx_set_sheet(fr_dmx* d, fr_ctx* ctx, int num_subs, const int32_t* row_dest, int n_rows,
                      const int32_t class_dest[4]) {
+    return fr_dmx_set_sheet2(d, ctx, num_subs, num_subs, row_dest, n_rows, class_dest);
+}
+
+int fr_dmx_set_sheet2(fr_dmx* d, fr_ctx* ctx, int num_subs1, int num_subs2, const int32_t* row_dest, int n_rows,
+                      const int32_t class_dest[4]) {
     if (!ctx || !class_dest || n_rows < 0 || (n_rows && !row_dest))
-        return d->err = "fr_dmx_set_sheet: null context or destinations", FR_ERR_INVALID;
+        return d->err = "fr_dmx_set_sheet[2]: null context or destinations", FR_ERR_INVALID;
     d->key_mode = false;
     int device = -1;
     SheetArgs sh{};
     NbrMap nm{};
-    if (int rc = borrow_sheet(ctx, num_subs, &device, &sh, &nm))
-        return d->err = std::string("fr_dmx_set_sheet: ") + fr_last_error(ctx), rc;
-    if (device != d->device) return d->err = "fr_dmx_set_sheet: the context is on another device", FR_ERR_INVALID;
+    if (int rc = borrow_sheet(ctx, num_subs1, num_subs2, &device, &sh, &nm))
+        return d->err = std::string("fr_dmx_set_sheet[2]: ") + fr_last_error(ctx), rc;
+    if (device != d->device) return d->err = "fr_dmx_set_sheet[2]: the context is on another device", FR_ERR_INVALID;
     if (n_rows != std::max(sh.S, 0))
-        return d->err = "fr_dmx_set_sheet: n_rows differs from the sheet's rows", FR_ERR_INVALID;
+        return d->err = "fr_dmx_set_sheet[2]: n_rows differs from the sheet's rows", FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     DK(hipStreamSynchronize(d->stream));  // an earlier window may still read the old destinations
     if (d->row_dest) DK(hipFree(d->row_dest));
@@ -507,7 +512,8 @@ int fr_dmx_set_sheet(fr_dmx* d, fr_ctx* ctx, int num_subs, const int32_t* row_de
     for (int k = 0; k < 4; ++k) d->class_dest.v[k] = class_dest[k];
     d->sheet = sh;
     d->nbr = nm;
-    d->nsubs = num_subs;
+    d->nsubs1 = num_subs1;
+    d->nsubs2 = num_subs2;
     d->key_mode = true;
     return FR_OK;
 }
@@ -548,8 +554,8 @@ static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_re
         hipLaunchKernelGGL(dmx_index<true>, dim3(std::min<u32>(ntiles, 4096)), dim3(DWG), 0, d->stream, buf, len,
                            ntiles, d->base, d->rs[mate], d->dest, DmxTable{nullptr, nullptr, 0}, d->rkey);
         DK(hipGetLastError());
-        DK(launch_dmx_classify(d->rkey, d->dest, nrec, d->sheet, d->nsubs, d->nbr, d->row_dest, d->class_dest,
-                               d->stream));
+        DK(launch_dmx_classify(d->rkey, d->dest, nrec, d->sheet, d->nsubs1, d->nsubs2, d->nbr, d->row_dest,
+                               d->class_dest, d->stream));
     } else if (ntiles) {
         DmxTable tab{d->tkeys, d->tvals, d->tmask};
         hipLaunchKernelGGL(dmx_index<false>, dim3(std::min<u32>(ntiles, 4096)), dim3(DWG), 0, d->stream, buf, len,

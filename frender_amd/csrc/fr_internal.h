@@ -265,9 +265,9 @@ struct ClassOut {
 
 enum { CLS_UNDET = 0, CLS_HOP = 1, CLS_DEMUX = 2, CLS_AMBIG = 3 };
 
-// Classify neighbourhood maps (fr_classify.hip, nbr_*), built per (sheet, nsubs): for each sheet list
-// (idx1, idx2, rc(idx2)) every packed code within nsubs substitutions of a distinct sheet value maps
-// to that value's id = the first row holding it; a code near several distinct values is marked
+// Classify neighbourhood maps (fr_classify.hip, nbr_*), built per (sheet, nsubs1, nsubs2): for each sheet list
+// (idx1 at radius nsubs1; idx2 and rc(idx2) at nsubs2) every packed code within the list's radius of a distinct
+// sheet value maps to that value's id = the first row holding it; a code near several distinct values is marked
 // (vmin != vmax) and classified by the exact row scan.  The pair maps give, per (idx1 id, idx2 id),
 // the rows holding both values: their count and first row.
 constexpr u64 NBR_KEY = 1ull << 63;  // occupied-slot bit of a map key (packed codes use <= 63 bits)
@@ -346,13 +346,14 @@ hipError_t launch_fin_rank(GSlot* slots, u64 nk, const BinMap& m, const u32* bas
 // o.err_first heads this call's block of error word + rc sums; the launch also zeroes the zero_n words of the
 // block the next call will use (zero_next), and a workgroup that meets a code with an error sets *err_flag
 // (pinned host memory, zeroed by the caller): only then does the host fetch the exact error word
-hipError_t launch_classify(const u64* keys, const u64* counts, u64 n, SheetArgs sh, int nsubs, int rc,
+hipError_t launch_classify(const u64* keys, const u64* counts, u64 n, SheetArgs sh, int nsubs1, int nsubs2, int rc,
                            ClassOut o, const NbrMap& nm, u64* zero_next, u32 zero_n, u64* err_flag, hipStream_t s);
 // neighbourhood codes of one sheet row: sum over d <= nsubs of C(L, d) 5^d (every query symbol)
 u64 nbr_codes_per_row(int L, int nsubs);
-// (re)build the maps of nm (already allocated and zeroed) for the sheet sh; canon = 3 x S value ids
-hipError_t launch_nbr_build(const SheetArgs& sh, const int32_t* canon, int nsubs, int rc, const NbrMap& nm,
-                            hipStream_t s);
+// (re)build the maps of nm (already allocated and zeroed) for the sheet sh; canon = 3 x S value ids.  The idx1
+// list is inserted at radius nsubs1, the idx2 and rc(idx2) lists at nsubs2
+hipError_t launch_nbr_build(const SheetArgs& sh, const int32_t* canon, int nsubs1, int nsubs2, int rc,
+                            const NbrMap& nm, hipStream_t s);
 // demux key mode (fr_demux.hip, fr_dmx_set_sheet): rec_dest[u] == DMX_PENDING marks a record whose fast key
 // dmx_index left in rec_key[u]; the launch replaces it with the record's destination: FR_DMX_NOPLUS /
 // FR_DMX_LEN1 / FR_DMX_LEN2 where classify_kernel reports error 3 / 1 / 2, row_dest[row] for a demuxable
@@ -361,12 +362,12 @@ constexpr int32_t DMX_PENDING = INT32_MIN;
 struct DmxClassDest {
     int32_t v[4];        // by CLS_*
 };
-hipError_t launch_dmx_classify(const u64* rec_key, int32_t* rec_dest, u64 n, SheetArgs sh, int nsubs,
+hipError_t launch_dmx_classify(const u64* rec_key, int32_t* rec_dest, u64 n, SheetArgs sh, int nsubs1, int nsubs2,
                                const NbrMap& nm, const int32_t* row_dest, DmxClassDest cd, hipStream_t s);
 hipError_t launch_classify_cp(int n, const u32* q1, const int32_t* q1len, const u32* q2, const int32_t* q2len,
                               int stride, int S, const u32* s1, const int32_t* s1len, const u32* s2,
-                              const int32_t* s2len, const u32* s2rc, const int32_t* name, int nsubs, int rc,
-                              ClassOut o, hipStream_t s);
+                              const int32_t* s2len, const u32* s2rc, const int32_t* name, int nsubs1, int nsubs2,
+                              int rc, ClassOut o, hipStream_t s);
 hipError_t launch_presence_scan(const GSlot* slots, u64 n, u32 tag, Presence* pres, u64 cap, DevState* st,
                                 hipStream_t s);
 hipError_t launch_merge(Table t, DevState* st, const u64* keys, const u64* counts, const u64* first, u64 n,
@@ -397,9 +398,9 @@ constexpr u64 BGZF_MAX_IN = 1ull << 30;  // compressed bytes of a BGZF file for 
 bool bgzf_member_table(const u8* data, size_t n, std::vector<BgzfMember>& out);
 // fr_deflate.hip: the operator "feed n zero bytes into the raw CRC-32 register", byte-sliced (4 x 256 words)
 void crc_shift_table(u64 n, u32* T);
-// fr_api.hip, for fr_dmx_set_sheet: the device sheet of ctx and its neighbourhood maps for nsubs (built by the
-// lazy builder when they are not current), complete on the device when the call returns
-int borrow_sheet(::fr_ctx* ctx, int nsubs, int* device, SheetArgs* sh, NbrMap* nm);
+// fr_api.hip, for fr_dmx_set_sheet: the device sheet of ctx and its neighbourhood maps for (nsubs1, nsubs2)
+// (built by the lazy builder when they are not current), complete on the device when the call returns
+int borrow_sheet(::fr_ctx* ctx, int nsubs1, int nsubs2, int* device, SheetArgs* sh, NbrMap* nm);
 
 // ---- the demux windows' tally (fr_dmx_tally.hip; fr_demux.hip's fr_dmx_tally_* entry points check the mode and
 // the call order and forward here).  Every call returns FR_OK or an FR_ERR_* code with its message in err; the

@@ -30,7 +30,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import demux_mode, get_indexes, gz_format, input_spec, parse_files, report_args, single_index
+from .host import (demux_mode, get_indexes, gz_format, input_spec, limits_of, mismatch_limits, num_subs_of,
+                   parse_files, report_args, single_index)
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
 # the column order `scan` itself writes (frender.py:482-501, report_analysis)
@@ -417,17 +418,18 @@ def sheet_destinations(sheet_ids, route_of) -> tuple:
 
 
 class SheetMode:
-    """`demux -b SHEET -n N`: every pair's code is classified against the sample sheet as `scan -n N`
-    classifies it (frender.py:214-291), per record on the GPU (fr_dmx_set_sheet); no results file.  This
-    object is the host's part: the sheet context of this process's GPU, the codes outside the fast
-    alphabet (case-folded, classified over code points as scan.process classifies exotic codes, each
-    distinct string once for the whole run) and the exceptions scan raises."""
+    """`demux -b SHEET -n N [--n1 A] [--n2 B]`: every pair's code is classified against the sample sheet as
+    `scan` with the same limits classifies it (frender.py:214-291), per record on the GPU (fr_dmx_set_sheet /
+    fr_dmx_set_sheet2); no results file.  This object is the host's part: the sheet context of this process's
+    GPU, the codes outside the fast alphabet (case-folded, classified over code points as scan.process classifies
+    exotic codes, each distinct string once for the whole run) and the exceptions scan raises."""
     _ERR = {_lib.FR_DMX_LEN1: 1, _lib.FR_DMX_LEN2: 2, _lib.FR_DMX_NOPLUS: 3}  # destination value <-> scan's error
 
-    def __init__(self, indexes: dict, num_subs: int, route_of, single: bool = False):
+    def __init__(self, indexes: dict, num_subs, route_of, single: bool = False):
         self.idx1, self.idx2, self.ids = indexes["idx1"], indexes["idx2"], indexes["id"]  # as uploaded, once bound
         self.single = bool(single)  # --single-index: a code is its idx1 alone, as scan.process(single=True) takes it
-        self.num_subs = int(num_subs)
+        # one int for both indexes, or a pair (n1, n2) when they differ (`--n1` / `--n2`, as scan.process takes it)
+        self.num_subs = num_subs_of(*(int(v) for v in limits_of(num_subs)))
         self.route_of = route_of
         self.memo = {}       # exotic code -> destination or FR_DMX_LEN1 / _LEN2 / _NOPLUS
         self.classified = 0  # exotic strings sent to the classifier (each distinct one once)
@@ -804,6 +806,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     report_path, prefix = report_args(args)
     fmt = gz_format(args)
     single = single_index(args)
+    num_subs = num_subs_of(*mismatch_limits(args)) if mode == "b" else None  # --n2 with --single-index: refused here
     samples = not args.no_samples
     level = getattr(args, "gz_level", None) or 9  # gzip.open's default, as the reference writes
     kind = writer_kind(getattr(args, "gz_writer", None) or "gpu", fmt)
@@ -836,7 +839,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     names, route_of = plan_destinations(ids, samples, not args.no_undeter, not args.no_index_hop, not args.no_ambiguous)
     # destination id -> writer pair (N ranks: its name; rank 0 writes the files at the end)
     writers = [open_files(name, args.d, infix, level, kind) for name in names] if group is None else names
-    sheet = SheetMode(indexes, args.n, route_of, single) if mode == "b" else None
+    sheet = SheetMode(indexes, num_subs, route_of, single) if mode == "b" else None
     lazy = set(range(len(ids))) if sheet is not None and samples else set()  # sample destinations (-b: kept if hit)
     hit = set()
     report = Report(report_path, prefix) if report_path is not None else None  # --report (with -b: report_args)

@@ -78,6 +78,36 @@ def single_index(args) -> bool:
     return single
 
 
+SINGLE_N2_REFUSAL = "--single-index and --n2 exclude each other: there is no index 2 to match (--n1 is allowed)"
+
+
+def mismatch_limits(args) -> tuple:
+    """(n1, n2) of a scan's or demux -b's arguments: the mismatches allowed in index 1 and in index 2 (and its
+    reverse complement).  --n1 / --n2 each default to -n (a namespace without the fields, as the reference's,
+    means not given).  --single-index refuses --n2, before anything is opened, and runs with n2 = n1."""
+    n, n1, n2 = getattr(args, "n", None), getattr(args, "n1", None), getattr(args, "n2", None)
+    single = bool(getattr(args, "single_index", False))
+    if single and n2 is not None:
+        raise SystemExit(SINGLE_N2_REFUSAL)
+    n1 = n if n1 is None else n1
+    n2 = n1 if single else n if n2 is None else n2
+    return n1, n2
+
+
+def num_subs_of(n1, n2):
+    """The num_subs argument of scan.process, seam.process, SheetMode and the context's classify calls: the one
+    int when both limits are equal (exactly the one-limit calls), else the pair (n1, n2)."""
+    return n1 if n1 == n2 else (n1, n2)
+
+
+def limits_of(num_subs) -> tuple:
+    """(n1, n2) of a num_subs argument: an int stands for both."""
+    if isinstance(num_subs, (tuple, list)):
+        n1, n2 = num_subs
+        return n1, n2
+    return num_subs, num_subs
+
+
 def get_indexes(barcode_file, single: bool = False) -> dict:
     """frender.py:90-116 — {"id": [...], "idx1": [...], "idx2": [...]} in sheet row order.  single
     (--single-index): no index-2 column is looked for, one that exists is ignored, every idx2 is ""."""
@@ -143,8 +173,8 @@ def reverse_complement(s: str) -> str:
 
 def demux_mode(args) -> str:
     """Where a demux's arguments take the classes from: "r", a scan's result file (-r), or "b", the sample
-    sheet itself (-b with -n).  Exactly one of the two; -n goes with -b only.  Called before anything is
-    opened or created (a namespace without a field means the flag was not given)."""
+    sheet itself (-b with -n).  Exactly one of the two; -n, --n1 and --n2 go with -b only.  Called before anything
+    is opened or created (a namespace without a field means the flag was not given)."""
     r, b, n = getattr(args, "r", None), getattr(args, "b", None), getattr(args, "n", None)
     if r is not None and b is not None:
         raise SystemExit("demux: -r and -b exclude each other (a scan's result file, or the sample sheet with -n)")
@@ -155,6 +185,9 @@ def demux_mode(args) -> str:
         raise SystemExit("demux -b: -n (mismatches allowed, as in scan) is required")
     if r is not None and n is not None:
         raise SystemExit("demux -r: -n belongs to -b (the result file already holds every code's class)")
+    for flag in ("n1", "n2"):
+        if r is not None and getattr(args, flag, None) is not None:
+            raise SystemExit(f"demux -r: --{flag} belongs to -b (the result file already holds every code's class)")
     return "r" if r is not None else "b"
 
 

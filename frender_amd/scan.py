@@ -33,8 +33,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import (SINGLE_RC_REFUSAL, find_barcode_file, get_cores, get_indexes, input_spec, parse_files,
-                   reverse_complement, single_index)
+from .host import (SINGLE_RC_REFUSAL, find_barcode_file, get_cores, get_indexes, input_spec, limits_of,
+                   mismatch_limits, num_subs_of, parse_files, reverse_complement, single_index)
 
 UNDET, HOP, DEMUX, AMBIG = 0, 1, 2, 3
 CLASS_NAMES = _lib.CLASS_NAMES
@@ -349,18 +349,21 @@ def split_exotic(codes, single: bool = False) -> tuple:
     return kept, q1, q2, bare
 
 
-def process(cores, table: UniqueTable, indexes: dict, num_subs: int, rc_mode: bool, ctx=None,
+def process(cores, table: UniqueTable, indexes: dict, num_subs, rc_mode: bool, ctx=None,
             single: bool = False) -> Results:
     """frender.py:391-426 on the GPU: classify every unique code (fast keys by packed
     Hamming, exotic codes by the code-point classifier); raise the reference's first error.
     On a key partition (multi-GPU): each rank classifies its partition; the -rc per-name sums are
     all-reduced and the first error in first-occurrence order over all partitions is raised.
+    num_subs: one int for both indexes, as the reference's, or a pair (n1, n2): idx1 is matched at n1
+    (frender.py:256), idx2 and rc(idx2) at n2 (:257); equal limits are passed on as the one int.
     single (--single-index, not in the reference): a code is code.split("+")[0] alone, classified as the
     reference classifies idx1 + "+" against a sheet whose idx2 are all "" (DESIGN.md §4.4); only idx1's
     length can be in error, and there is no -rc."""
     ctx = ctx or default_context()
     if single and rc_mode:
         raise SystemExit(SINGLE_RC_REFUSAL)
+    num_subs = num_subs_of(*limits_of(num_subs))
     idx1, idx2, ids, names, name_id = upload_sheet(ctx, indexes, single)
     if cores > 1 and _lead(table):
         print(f"Multiprocessing with {cores} cores")
@@ -666,7 +669,9 @@ def report_analysis(table: UniqueTable, results: Results, demux_ok, out_csv_name
 
 
 def output_name(num_subs, user_infix, files_arg):
-    """frender.py:587-601."""
+    """frender.py:587-601.  A pair of unequal limits (n1, n2) is named n1+n2."""
+    n1, n2 = limits_of(num_subs)
+    num_subs = n1 if n1 == n2 else f"{n1}+{n2}"
     spec = input_spec(files_arg)
     if "dir" in spec:
         tail = spec["dir"].parts[-1]
@@ -679,9 +684,9 @@ def output_name(num_subs, user_infix, files_arg):
 
 def frender_scan(args, ctx=None) -> dict:
     """frender.py:567-642 with the hot path on the GPU."""
-    num_subs = args.n
     rc_mode = args.rc
     single = single_index(args)  # with -rc: refused here, before any file is opened
+    num_subs = num_subs_of(*mismatch_limits(args))  # -n, --n1, --n2 (--n2 with --single-index: refused here)
     cores = get_cores(args.c)
     sample = args.s
     user_infix = args.o if args.o else ""

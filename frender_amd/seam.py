@@ -223,7 +223,8 @@ def tally_barcodes(cores, files, sample=None, ctx=None) -> BarcodeCounter:
 
 def process(cores, barcode_counter, indexes, num_subs, rc_mode, ctx=None, single=False) -> ResultsMapping:
     """frender.py:391-426 on the GPU (frender_amd.scan.process), the reference's shape.  single: a
-    single-indexed library (indexes from get_indexes(sheet, single=True); not in the reference)."""
+    single-indexed library (indexes from get_indexes(sheet, single=True); not in the reference).  num_subs: the
+    reference's one int, or a pair (n1, n2) of limits for index 1 and index 2 (not in the reference)."""
     table, index = _table_of(barcode_counter)
     return ResultsMapping(table, _scan.process(cores, table, indexes, num_subs, rc_mode, ctx=ctx, single=single),
                           index)

@@ -112,7 +112,10 @@ int fr_sync(fr_ctx* ctx);
  * 8 phase stamps, speculation replays, exotic-only replays, next full-chunk size, heavy launches,
  * big-feed rollbacks, the last device feed's fullest launch-log fold, its fold overflows, its range bytes,
  * memsets and copies queued on the context's stream since the last fr_reset (each a blit dispatch of its own:
- * a steady one-file fr_feed_device step queues none)}.  New entries are added at the end. */
+ * a steady one-file fr_feed_device step queues none), 1 when the classify neighbourhood maps were on for the
+ * context's last fr_classify / fr_classify2 / fr_dmx_set_sheet* (0: every code took the row scan); a call that
+ * is refused for its arguments before it looks at the maps (no sheet, rc_mode on a single-index sheet) leaves
+ * the entry as the call before it set it}.  New entries are added at the end. */
 int fr_get_diag(fr_ctx* ctx, uint64_t* out, int n);
 
 /* ---- sample sheet (the idx1/idx2/id lists of get_indexes, frender.py:90-116) -------
@@ -302,6 +305,14 @@ int fr_classify(fr_ctx* ctx, int num_subs, int rc_mode,
                 int16_t* m1, int16_t* m2, uint8_t* cls, int16_t* row,
                 int16_t* rc_m2, uint8_t* rc_cls, int16_t* rc_row,
                 int64_t* err_unique, int32_t* err_which);
+/* The same with a mismatch limit per index: idx1 is matched against the sheet's idx1 list with num_subs1
+ * (:256), idx2 against the idx2 list -- and, with rc_mode, the rc(idx2) list -- with num_subs2 (:257); the
+ * class rule, the rc call, the asserts and the outputs are fr_classify's.  A negative limit matches no row of
+ * its list.  fr_classify(n) is fr_classify2(n, n). */
+int fr_classify2(fr_ctx* ctx, int num_subs1, int num_subs2, int rc_mode,
+                 int16_t* m1, int16_t* m2, uint8_t* cls, int16_t* row,
+                 int16_t* rc_m2, uint8_t* rc_cls, int16_t* rc_row,
+                 int64_t* err_unique, int32_t* err_which);
 /* per distinct name: reads demuxable with fwd idx2 / with rc idx2 (:367-373), from the
  * last rc_mode classify */
 int fr_rc_counts(fr_ctx* ctx, uint64_t* reads_f, uint64_t* reads_rc);
@@ -311,6 +322,11 @@ int fr_classify_cp(fr_ctx* ctx, int n, const uint32_t* q1, const int32_t* q1len,
                    const uint32_t* q2, const int32_t* q2len, int cp_stride, int num_subs, int rc_mode,
                    int16_t* m1, int16_t* m2, uint8_t* cls, int16_t* row,
                    int16_t* rc_m2, uint8_t* rc_cls, int16_t* rc_row, int32_t* err_which);
+/* the same with a limit per index, as fr_classify2; fr_classify_cp(n) is fr_classify_cp2(n, n) */
+int fr_classify_cp2(fr_ctx* ctx, int n, const uint32_t* q1, const int32_t* q1len,
+                    const uint32_t* q2, const int32_t* q2len, int cp_stride, int num_subs1, int num_subs2,
+                    int rc_mode, int16_t* m1, int16_t* m2, uint8_t* cls, int16_t* row,
+                    int16_t* rc_m2, uint8_t* rc_cls, int16_t* rc_row, int32_t* err_which);
 
 /* ---- multi-GPU merge: export / import the compacted table ----------- */
 int fr_export_unique_device(fr_ctx* ctx, void* dev_keys, void* dev_counts, void* dev_first, uint64_t cap);
@@ -365,6 +381,10 @@ int fr_dmx_set_table(fr_dmx* d, const uint64_t* keys, const int32_t* vals, uint6
  * classifies on it with no other num_subs.  fr_dmx_set_table switches back to table mode. */
 int fr_dmx_set_sheet(fr_dmx* d, fr_ctx* ctx, int num_subs, const int32_t* row_dest, int n_rows,
                      const int32_t class_dest[4]);
+/* the same with a limit per index, as fr_classify2 classifies (the borrowed maps are those of the pair);
+ * fr_dmx_set_sheet(n) is fr_dmx_set_sheet2(n, n) */
+int fr_dmx_set_sheet2(fr_dmx* d, fr_ctx* ctx, int num_subs1, int num_subs2, const int32_t* row_dest, int n_rows,
+                      const int32_t class_dest[4]);
 /* mate 0 = R1, 1 = R2 (R2 also resolves every record's destination); returns the record count */
 int fr_dmx_load(fr_dmx* d, int mate, const uint8_t* data, uint64_t len, uint64_t* n_records);
 /* the same over the concatenation of n_parts host buffers (a window without a host-side join) */
