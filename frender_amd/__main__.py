@@ -88,6 +88,11 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("-p", metavar="fix_prefix",
                    help="with --report: when matching sample ids to filenames for demux_ok, remove this prefix from "
                         "the sample id (scan's -p)")
+    d.add_argument("--stats", metavar="stats_csv",
+                   help="also write a CSV of what every output got, per read (R1, R2): reads, bases, bases >= Q30, "
+                        "quality bytes and their Phred sum, mean quality, %% >= Q30 and %% of the reads; a row pair "
+                        "per planned output, samples without reads included; summed on the GPU in the same pass "
+                        "(-r and -b)")
     d.add_argument("--strict-header", action="store_true",
                    help="reject a results file in scan's own column order, as frender.py does (default: accept it)")
     d.add_argument("--gz-level", type=int, default=None,
@@ -136,10 +141,11 @@ def main(argv=None):
         frender_scan(args)
         return 0
     if getattr(args, "cmd", None) == "demux":
-        from .host import demux_mode, gz_format, mismatch_limits, report_args
+        from .host import demux_mode, gz_format, mismatch_limits, report_args, stats_path
         try:
             demux_mode(args)  # -r or -b with -n, before ranks start (frender_demux checks it too)
             report_args(args)  # --report with -b, -p with --report
+            stats_path(args)  # --stats and --report name two files
             mismatch_limits(args)  # --n2 with --single-index
         except SystemExit as e:
             parser.error(str(e))

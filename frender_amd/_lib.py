@@ -171,6 +171,9 @@ _SIGS = {
     "fr_dmx_tally_sizes": (C.c_int, [P, u64p, u64p]),
     "fr_dmx_tally_get": (C.c_int, [P, P, P, P, P, P, P]),
     "fr_dmx_tally_rows_device": (C.c_int, [P, P, C.c_uint64]),
+    "fr_dmx_stats_begin": (C.c_int, [P, C.c_int]),
+    "fr_dmx_stats_window": (C.c_int, [P, C.c_uint64]),
+    "fr_dmx_stats_get": (C.c_int, [P, C.c_int, P]),
     "fr_defl_create": (P, [C.c_int]),
     "fr_defl_destroy": (None, [P]),
     "fr_defl_last_error": (C.c_char_p, [P]),
@@ -614,6 +617,21 @@ class Demux:
     def tally_rows_device(self, dev_ptr: int, cap: int):
         """The tally's (key, count, first) rows as int64 [n][3] at dev_ptr (cap rows): Context.merge_rows_at's form."""
         self._ck(lib.fr_dmx_tally_rows_device(self.h, P(dev_ptr), int(cap)), "fr_dmx_tally_rows_device")
+
+    # ---- the windows' per-output statistics (demux --stats; fr_dmx_stats_*) ----------------
+    def stats_begin(self, n_dest: int):
+        self._ck(lib.fr_dmx_stats_begin(self.h, int(n_dest)), "fr_dmx_stats_begin")
+
+    def stats_window(self, n_pairs: int):
+        """Add the n_pairs record pairs the last route() routed to the per-destination sums."""
+        self._ck(lib.fr_dmx_stats_window(self.h, int(n_pairs)), "fr_dmx_stats_window")
+
+    def stats_get(self, n_dest: int) -> np.ndarray:
+        """uint64 [2, n_dest, 5]: per mate and destination (reads, bases, quality_bytes, q30_bases,
+        quality_raw_sum)."""
+        out = np.zeros((2, max(int(n_dest), 0), 5), np.uint64)
+        self._ck(lib.fr_dmx_stats_get(self.h, int(n_dest), _ptr(out)), "fr_dmx_stats_get")
+        return out
 
 
 class Deflater:

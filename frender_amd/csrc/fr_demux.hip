@@ -15,6 +15,8 @@
 //              gather-copy of both mates' record bytes into destination-major buffers
 // With fr_dmx_tally_begin (sheet mode, `demux -b --report`) the routed records' keys are also counted: the kernels
 // and their tables are fr_dmx_tally.hip's, the entry points at the end of this file check mode and call order.
+// With fr_dmx_stats_begin (`demux --stats`) the routed records are also summed per destination (reads, bases, quality):
+// fr_dmx_stats.hip's kernel over the routed bytes, entered the same way.
 // The host inflates, normalises universal newlines (frender.py:776 reads in text mode), resolves
 // the rare codes outside the fast alphabet, raises the reference's errors, and gzips each
 // destination's bytes into its writer pair.
@@ -405,6 +407,10 @@ struct fr_dmx {
     // no fr_dmx_tally_window has counted yet
     DmxTally* tally = nullptr;
     u64 routed_ok = 0;
+    // the windows' statistics (fr_dmx_stats_begin; fr_dmx_stats.hip), and the pairs the last fr_dmx_route routed
+    // that no fr_dmx_stats_window has added yet
+    DmxStats* stats = nullptr;
+    u64 stats_ok = 0;
 };
 
 #define DK(x)                                                                  \
@@ -449,6 +455,7 @@ void fr_dmx_destroy(fr_dmx* d) {
         if (x) (void)hipFree(x);
     for (fr_defl* z : d->defl) fr_defl_destroy(z);
     dmx_tally_destroy(d->tally);
+    dmx_stats_destroy(d->stats);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
 }
@@ -521,7 +528,7 @@ int fr_dmx_set_sheet2(fr_dmx* d, fr_ctx* ctx, int num_subs1, int num_subs2, cons
 static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_records) {
     d->src[mate] = buf;
     d->len[mate] = len;
-    d->routed_ok = 0;
+    d->routed_ok = d->stats_ok = 0;
     const u32 ntiles = (u32)((len + DT - 1) / DT);
     DK(ensure(&d->cnt, d->c_cnt, (u64)ntiles + 1));
     DK(ensure(&d->base, d->c_base, (u64)ntiles + 1));
@@ -658,7 +665,7 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     if (P >= 0xFFFFFFFFull) return d->err = "too many records in one file pair", FR_ERR_CAPACITY;
     *first_error = -1;
     *error_val = 0;
-    d->routed_ok = 0;
+    d->routed_ok = d->stats_ok = 0;
     for (int k = 0; k < n_dest; ++k) bytes_r1[k] = bytes_r2[k] = 0;
     d->out_len[0] = d->out_len[1] = 0;
     d->hoff[0].assign((size_t)std::max(n_dest, 0) + 1, 0);
@@ -735,7 +742,7 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     d->out_len[1] = s2;
     d->hoff[0] = h1;
     d->hoff[1] = h2;
-    d->routed_ok = P;
+    d->routed_ok = d->stats_ok = P;
     return FR_OK;
 }
 
@@ -786,6 +793,35 @@ int fr_dmx_tally_rows_device(fr_dmx* d, void* dev_rows, uint64_t cap) {
     if (int rc = tally_ready(d, "fr_dmx_tally_rows_device")) return rc;
     DK(hipSetDevice(d->device));
     return dmx_tally_rows_device(d->tally, dev_rows, cap, d->err);
+}
+
+// ---- the windows' statistics: the call order is checked here, the work is fr_dmx_stats.hip's
+int fr_dmx_stats_begin(fr_dmx* d, int n_dest) {
+    DK(hipSetDevice(d->device));
+    DK(hipStreamSynchronize(d->stream));  // an earlier window's sums may still be queued on the old accumulators
+    d->stats_ok = 0;
+    return dmx_stats_begin(&d->stats, d->device, d->stream, n_dest, d->err);
+}
+
+int fr_dmx_stats_window(fr_dmx* d, uint64_t n_pairs) {
+    if (!d->stats) return d->err = "fr_dmx_stats_window: no fr_dmx_stats_begin", FR_ERR_INVALID;
+    if (n_pairs != d->stats_ok)
+        return d->err = "fr_dmx_stats_window: n_pairs differs from the pairs the last fr_dmx_route routed (or they "
+                        "are added already)", FR_ERR_INVALID;
+    if (d->hoff[0].size() > (size_t)dmx_stats_n_dest(d->stats) + 1)
+        return d->err = "fr_dmx_stats_window: the last fr_dmx_route had more destinations than fr_dmx_stats_begin",
+               FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    d->stats_ok = 0;
+    return dmx_stats_window(d->stats, d->out[0], d->out[1], d->o1, d->l1, d->o2, d->l2, d->k_out, n_pairs, d->err);
+}
+
+int fr_dmx_stats_get(fr_dmx* d, int n_dest, uint64_t* out) {
+    if (!d->stats) return d->err = "fr_dmx_stats_get: no fr_dmx_stats_begin", FR_ERR_INVALID;
+    if (n_dest != dmx_stats_n_dest(d->stats))
+        return d->err = "fr_dmx_stats_get: n_dest differs from fr_dmx_stats_begin", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    return dmx_stats_get(d->stats, out, d->err);
 }
 
 // the routed bytes of a mate through its fr_defl: gzip streams (crc32 set) or BGZF member runs

@@ -415,4 +415,16 @@ int dmx_tally_get(DmxTally* t, u64* keys, u64* counts, u64* first, u32* pres_uni
                   std::string& err);
 int dmx_tally_rows_device(DmxTally* t, void* dev_rows, u64 cap, std::string& err);
 
+// ---- the demux windows' per-output statistics (fr_dmx_stats.hip; fr_demux.hip's fr_dmx_stats_* entry points check
+// the call order and forward here, as for the tally).  acc[2][n_dest][5] u64 in HBM, owned by DmxStats.  out1/out2:
+// the routed bytes of the mates (16 bytes of slack past the last record); o/l: every record's offset and length in
+// partition order; dest: the sorted destination per partition position; n: the pairs routed.
+struct DmxStats;
+int dmx_stats_begin(DmxStats** t, int device, hipStream_t stream, int n_dest, std::string& err);
+void dmx_stats_destroy(DmxStats* t);
+int dmx_stats_n_dest(const DmxStats* t);
+int dmx_stats_window(DmxStats* t, const u8* out1, const u8* out2, const u64* o1, const u64* l1, const u64* o2,
+                     const u64* l2, const u32* dest, u64 n, std::string& err);
+int dmx_stats_get(DmxStats* t, u64* out, std::string& err);
+
 }  // namespace fr

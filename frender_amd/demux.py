@@ -11,6 +11,9 @@ errors and gzips each destination's bytes into its writer pair (threads: zlib re
 against the sample sheet as `scan -n N` classifies it (fr_dmx_set_sheet, SheetMode below) and the rest is
 the same, so one pass over the inputs writes what scan + demux -r write in two.  With `--report PATH` the same
 pass also counts every distinct code (fr_dmx_tally_*, Report below) and writes scan's results CSV to PATH.
+
+`--stats PATH` (both modes): the same pass sums what every output got, per mate -- reads, bases, quality bytes,
+bases >= Q30 and the quality sum -- over the routed records on the GPU (fr_dmx_stats_*, Stats below).
 """
 from __future__ import annotations
 
@@ -31,7 +34,7 @@ import numpy as np
 
 from . import _lib
 from .host import (demux_mode, get_indexes, gz_format, input_spec, limits_of, mismatch_limits, num_subs_of,
-                   parse_files, report_args, single_index)
+                   parse_files, report_args, single_index, stats_path)
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
 # the column order `scan` itself writes (frender.py:482-501, report_analysis)
@@ -639,14 +642,84 @@ class Report:
             ctx.close()
 
 
+STATS_HEADER = ["output", "read", "reads", "bases", "q30_bases", "quality_bytes", "quality_sum", "mean_quality",
+                "pct_q30", "pct_reads"]
+STATS_FIELDS = ("reads", "bases", "quality_bytes", "q30_bases", "quality_raw_sum")  # fr_dmx_stats_get's order
+
+
+class Stats:
+    """`demux --stats PATH`: what every output got, per mate.  The GPU sums the records of every routed window per
+    destination (Demux.stats_*: fr_dmx_stats.hip) -- a record is the loader's (up to four lines), its second line
+    the sequence and its fourth the quality -- and this object turns the sums into the CSV: two rows (R1, R2) per
+    planned destination, in plan_destinations' order, a sample without reads included."""
+
+    def __init__(self, path=None):
+        self.path = None if path is None else str(path)
+        self.n_dest = 0
+
+    def begin(self, dmx, n_dest: int):
+        self.n_dest = int(n_dest)
+        dmx.stats_begin(self.n_dest)
+
+    def window(self, dmx, n_pairs: int):
+        """The window's first n_pairs records are routed, and still resident: add them."""
+        dmx.stats_window(n_pairs)
+
+    def local(self, dmx) -> np.ndarray:
+        """This process's sums once its last pair is done: uint64 [2, n_dest, 5] in STATS_FIELDS' order."""
+        return dmx.stats_get(self.n_dest)
+
+    @staticmethod
+    def sum_ranks(arrays) -> np.ndarray:
+        """The sums of several ranks as one (they are all counts): [2, n_dest, 5]."""
+        return np.sum([np.asarray(a, dtype=np.uint64) for a in arrays], axis=0, dtype=np.uint64)
+
+    @staticmethod
+    def rows(names, array) -> list:
+        """The CSV's rows without the header.  quality_sum = quality_raw_sum - 33 * quality_bytes (Phred+33; it is
+        negative when the bytes are below '!'); a derived column whose denominator is 0 is left empty."""
+        a = np.asarray(array)
+        assert a.shape == (2, len(names), len(STATS_FIELDS)), "stats: the array is not [2, destinations, 5]"
+
+        def ratio(num, den, scale=1):
+            return f"{scale * num / den:.2f}" if den else ""
+
+        out = []
+        totals = [sum(int(v) for v in a[m, :, 0]) for m in (0, 1)]
+        for k, name in enumerate(names):
+            for m, read in enumerate(("R1", "R2")):
+                reads, bases, qbytes, q30, raw = (int(v) for v in a[m, k])
+                qsum = raw - 33 * qbytes
+                out.append([name, read, reads, bases, q30, qbytes, qsum, ratio(qsum, qbytes), ratio(q30, qbytes, 100),
+                            ratio(reads, totals[m], 100)])
+        return out
+
+    def write(self, path, names, array):
+        with open(path, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(STATS_HEADER)
+            w.writerows(self.rows(names, array))
+
+    def write_ranks(self, group, wire, array, names):
+        """`--gpus N`, no rank failed: every rank's sums go to rank 0, which adds them and writes the file."""
+        import torch
+
+        from .dist import gather_rows
+        got = gather_rows(group, wire, torch.from_numpy(np.ascontiguousarray(array).view(np.int64).reshape(-1, 5)))
+        if group.get_rank() != 0:
+            return
+        shape = (2, len(names), len(STATS_FIELDS))
+        self.write(self.path, names, self.sum_ranks([g.view(np.uint64).reshape(shape) for g in got]))
+
+
 def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of, writers, window, sheet=None,
-                hit=None, report=None):
+                hit=None, report=None, stats=None):
     """One R1/R2 pair in record-aligned windows: the GPU indexes both windows, the complete
     record pairs are routed, and the bytes after the last routed record carry into the next
     window.  Pairing stops when either mate runs out of records (zip, frender.py:777).  The mates
     inflate on the native pool gz (files i1, i2).  sheet (SheetMode): `demux -b`, no results; hit: a set
     that collects the destinations pairs were routed to; report (Report, after its begin_pair): `--report`, every
-    routed window is counted."""
+    routed window is counted; stats (Stats, after its begin): `--stats`, every routed window is summed."""
     streams =[text_chunks(read1_file, gz, i1), text_chunks(read2_file, gz, i2)]
     bufs = [[], []]  # each mate's window as a list of decoded blocks (never joined on the host)
     eof = [False, False]
@@ -697,6 +770,8 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 raise SystemExit("Unrecognized read type found in supplied frender result file!")
             if report is not None:  # routed: these n_pairs records are in the output files, and in the table
                 report.window(dmx, n_pairs, ex, codes)
+            if stats is not None:  # queued behind the route, on the bytes it gathered
+                stats.window(dmx, n_pairs)
             if hit is not None:
                 hit.update(np.nonzero(b1 + b2)[0].tolist())
             # each mate's bytes for the files and their per-destination sizes, as the writers' family makes them
@@ -804,6 +879,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     t_start = time.perf_counter()
     mode = demux_mode(args)
     report_path, prefix = report_args(args)
+    stats_file = stats_path(args)
     fmt = gz_format(args)
     single = single_index(args)
     num_subs = num_subs_of(*mismatch_limits(args)) if mode == "b" else None  # --n2 with --single-index: refused here
@@ -843,6 +919,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     lazy = set(range(len(ids))) if sheet is not None and samples else set()  # sample destinations (-b: kept if hit)
     hit = set()
     report = Report(report_path, prefix) if report_path is not None else None  # --report (with -b: report_args)
+    stats = Stats(stats_file) if stats_file is not None else None  # --stats
 
     table = None
     if mode == "r":
@@ -855,23 +932,28 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     window = int(getattr(args, "window", None) or (512 << 20))  # decoded bytes per mate per GPU pass
     if group is not None:
         return _demux_ranks(group, args, pairs, results, route_of, table, writers, window, level, infix, kind, sheet,
-                            lazy, t_start, report)
+                            lazy, t_start, report, stats)
     paths = [str(f) for pr in pairs for f in pr]
     try:
         with _session(t_start, paths, kind, len(writers), _device_index(None), sheet, table, dev, ctx,
                       lambda: _close_writers(writers, names, lazy, hit, args.d, infix)) as (dmx, pool, gz):
             if report is not None:
                 report.begin(dmx)
+            if stats is not None:
+                stats.begin(dmx, len(names))
             for k, (read1_file, read2_file) in enumerate(pairs):
                 print(f"Demultiplexing {read1_file.name}...")
                 if report is not None:
                     report.begin_pair(dmx, k)
                 _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers,
-                            window, sheet, hit, report)
+                            window, sheet, hit, report, stats)
             if sheet is not None and samples and not (hit & lazy):
                 print(NO_SAMPLES_WARNING)  # known only now: no pair was demuxable
             if report is not None:  # every pair is routed: the table is complete
                 report.write_local(dmx, sheet, [str(os.path.basename(r1)) for r1, _ in pairs])
+            if stats is not None:
+                print(f"Writing demux statistics to {stats.path}")
+                stats.write(stats.path, names, stats.local(dmx))
     finally:
         STAGE_TIMES["total"] = time.perf_counter() - t_start
         if getattr(args, "stage_times", False):
@@ -928,7 +1010,7 @@ def _mkdir_everywhere(group, path):
 
 
 def _demux_ranks(group, args, pairs, results, route_of, table, names, window, level, infix, kind, sheet, lazy,
-                 t_start, report=None):
+                 t_start, report=None, stats=None):
     import shutil
 
     from .dist import PeerFailed, reduce_min
@@ -937,6 +1019,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
     mine = list(range(rank, len(pairs), world))
     failed, exc = len(pairs), None
     tally = None  # --report: this rank's table, once its last pair is done
+    sums = None  # --stats: this rank's sums, once its last pair is done
     try:
         # the session opens inside the try: a rank whose pool or device fails still joins the collectives below
         # (-b: this rank's own sheet context: classification is stateless, nothing is exchanged)
@@ -944,6 +1027,8 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                       sheet, table) as (dmx, pool, gz):
             if report is not None:
                 report.begin(dmx)
+            if stats is not None:
+                stats.begin(dmx, len(names))
             for j, k in enumerate(mine):
                 d = os.path.join(parts, str(k))
                 os.makedirs(d, exist_ok=True)
@@ -953,7 +1038,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                     if report is not None:
                         report.begin_pair(dmx, k)  # the global pair index: the ordinals are the one-process run's
                     _demux_pair(dmx, pool, gz, 2 * j, 2 * j + 1, pairs[k][0], pairs[k][1], results, route_of, writers,
-                                window, sheet, hit, report)
+                                window, sheet, hit, report, stats)
                 except (Exception, SystemExit) as e:  # re-raised below if it is the first in pair order
                     failed, exc = k, e
                 finally:
@@ -962,6 +1047,8 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                     break
             if report is not None and exc is None:
                 tally = report.local(dmx)
+            if stats is not None and exc is None:
+                sums = stats.local(dmx)
     except (Exception, SystemExit) as e:  # before any pair (the device, the table): this rank's first pair
         if exc is None:
             failed, exc = (mine[0] if mine else len(pairs)), e
@@ -1001,3 +1088,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
     if report is not None:  # no rank failed: every rank has its table
         report.write_ranks(group, _wire(group), tally, [str(os.path.basename(r1)) for r1, _ in pairs], sheet,
                            _device_index(group))
+    if stats is not None:  # after the output files are assembled, and after everything else the command prints
+        if rank == 0:
+            print(f"Writing demux statistics to {stats.path}")
+        stats.write_ranks(group, _wire(group), sums, names)

@@ -203,6 +203,18 @@ def report_args(args) -> tuple:
     return path, prefix or ""
 
 
+def stats_path(args):
+    """--stats PATH of a demux's arguments, or None (a namespace without the field has no statistics: the
+    reference's namespaces).  It cannot be --report's file.  Called with report_args, before anything is opened or
+    created."""
+    path = getattr(args, "stats", None)
+    report = getattr(args, "report", None)
+    if path is not None and report is not None and \
+            os.path.abspath(os.fspath(path)) == os.path.abspath(os.fspath(report)):
+        raise SystemExit("demux --stats: the statistics and --report cannot be written to the same file")
+    return path
+
+
 def gz_format(args) -> str:
     """--gz-format of a demux's arguments (a namespace without it means gzip), checked against --gz-writer:
     only the GPU writer makes BGZF.  Called before anything is opened or created."""

@@ -455,6 +455,24 @@ int fr_dmx_tally_get(fr_dmx* d, uint64_t* keys, uint64_t* counts, uint64_t* firs
  * fr_merge_rows_device takes; complete when the call returns. */
 int fr_dmx_tally_rows_device(fr_dmx* d, void* dev_rows, uint64_t cap);
 
+/* ---- the demux windows' per-output statistics (`demux --stats`; fr_dmx_stats.hip): what every destination got,
+ * per mate, summed over the routed records while they are resident: table mode and sheet mode alike.  A record
+ * is fr_dmx_records' byte span (up to four lines; a file's partial last group counts); split at its '\n', its
+ * second piece is the sequence and its fourth the quality line (absent pieces are empty).  Per record:
+ * reads += 1, bases += the sequence's length, quality_bytes += the quality line's length, q30_bases += its bytes
+ * with unsigned value >= 63 ('?', Phred+33 Q30), quality_raw_sum += its unsigned byte values (no byte is
+ * special; the caller subtracts 33 per quality byte).  Every call below returns FR_ERR_INVALID, with the sums
+ * untouched, when the order described is not kept. */
+/* Start (or clear) the statistics of a demux: n_dest destinations, all sums zero.  Off until this call. */
+int fr_dmx_stats_begin(fr_dmx* d, int n_dest);
+/* Add the n_pairs record pairs the last fr_dmx_route routed (it found no negative destination; n_pairs must be
+ * its count; a window is added once; before the next fr_dmx_load*; that route's n_dest is at most the begun
+ * one).  Queues on the context's stream and makes no synchronisation of its own. */
+int fr_dmx_stats_window(fr_dmx* d, uint64_t n_pairs);
+/* out[2][n_dest][5]: per mate and destination {reads, bases, quality_bytes, q30_bases, quality_raw_sum}; n_dest
+ * as begun.  Synchronises. */
+int fr_dmx_stats_get(fr_dmx* d, int n_dest, uint64_t* out);
+
 /* ---- GPU deflate over any byte ranges (fr_deflate.hip; fr_dmx_deflate runs it on the routed bytes).
  * Stream s is bytes [offsets[s], offsets[s + 1]) of the device buffer dev_data (4-byte aligned, 16
  * readable bytes past offsets[n_streams]); every stream becomes one raw deflate stream, no larger than

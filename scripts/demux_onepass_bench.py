@@ -14,12 +14,16 @@ output file of the two routes is compared (the first runs').  Every demux runs w
 per-window load+index and route stages of `demux -b`, of this tree's `demux -r` and, with --parent ROOT (a
 built checkout of the parent commit), of the parent's `demux -r` on the same inputs and results file come
 from the same alternating rounds.  With --report-arm, `demux -b --report` joins the same rounds: it replaces
-scan + demux -r, so that is its comparison, and its CSV is compared with the scan's (the first runs').  Writes one
-JSON document (--out), stamped with the tree's source hash.
+scan + demux -r, so that is its comparison, and its CSV is compared with the scan's (the first runs').  With
+--stats-arm, `demux -b --stats` joins the rounds: its comparison is `demux -b` without the flag on this tree (the
+flag's cost is the difference) and, with --parent, the parent's `demux -b`, which this tree's must equal without the
+flag; its output files are compared with the one-pass run's.  Writes one JSON document (--out), stamped with the
+tree's source hash.
 
 Needs a GPU: there is no CPU path to time.
 """
 import argparse
+import csv
 import gzip
 import hashlib
 import json
@@ -81,6 +85,9 @@ def main():
     ap.add_argument("--parent", help="root of a built checkout of the parent commit (its demux -r is timed too)")
     ap.add_argument("--report-arm", action="store_true", help="also time demux -b --report (the results CSV from "
                                                                "the same pass) in the same rounds")
+    ap.add_argument("--stats-arm", action="store_true", help="also time demux -b --stats (the per-output table from "
+                                                              "the same pass) and, with --parent, the parent's demux "
+                                                              "-b in the same rounds")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "demux_sheet_bench.json"))
     ap.add_argument("--workdir", help="where the inputs and outputs go (default: a temporary directory)")
     args = ap.parse_args()
@@ -131,6 +138,23 @@ def main():
                          os.path.join(w, "out"), "--stage-times", *allf], w, ROOT)
             return {"total_s": t, "stages": st, "dir": w, "csv": os.path.join(w, "report.csv")}
 
+        def stats_pass():
+            serial[0] += 1
+            w = os.path.join(d, f"sta_{serial[0]}")
+            os.mkdir(w)
+            t, st = run(["demux", "-b", sheet_csv, "-n", "1", "--stats", os.path.join(w, "stats.csv"), "-d",
+                         os.path.join(w, "out"), "--stage-times", *allf], w, ROOT)
+            return {"total_s": t, "stages": st, "dir": w, "csv": os.path.join(w, "stats.csv")}
+
+        def parent_one_pass(root):
+            serial[0] += 1
+            w = os.path.join(d, f"pone_{serial[0]}")
+            os.mkdir(w)
+            t, st = run(["demux", "-b", sheet_csv, "-n", "1", "-d", os.path.join(w, "out"), "--stage-times", *allf], w,
+                        root)
+            shutil.rmtree(w)
+            return {"total_s": t, "stages": st}
+
         def demux_r(root, csv_path):
             serial[0] += 1
             w = os.path.join(d, f"r_{serial[0]}")
@@ -148,13 +172,22 @@ def main():
             with open(cold["report"]["csv"], "rb") as f, open(cold["two_pass"]["csv"], "rb") as g:
                 report_doc = {"outputs_equal": digests(os.path.join(cold["report"]["dir"], "out")) == da,
                               "csv_equals_scan_csv": f.read() == g.read()}
+        stats_doc = None
+        if args.stats_arm:
+            cold["stats"] = stats_pass()
+            with open(cold["stats"]["csv"], newline="") as f:
+                rows = list(csv.DictReader(f))
+            stats_doc = {"outputs_equal": digests(os.path.join(cold["stats"]["dir"], "out")) == db,
+                         "csv_rows": len(rows),
+                         "csv_reads": {m: sum(int(r["reads"]) for r in rows if r["read"] == m) for m in ("R1", "R2")}}
         csv_path = os.path.join(d, "results.csv")
         shutil.copy(cold["two_pass"]["csv"], csv_path)
         out_files = len(da)
         for c in cold.values():
             shutil.rmtree(c["dir"])
-        warm = {"two_pass": [], "one_pass": [], "report": [], "parent_demux_r": []}
-        arms = (("two_pass", two_pass), ("one_pass", one_pass)) + ((("report", report_pass),) if args.report_arm else ())
+        warm = {"two_pass": [], "one_pass": [], "report": [], "stats": [], "parent_demux_r": [], "parent_one_pass": []}
+        arms = (("two_pass", two_pass), ("one_pass", one_pass)) + ((("report", report_pass),) if args.report_arm else ()) \
+            + ((("stats", stats_pass),) if args.stats_arm else ())
         for _ in range(max(args.runs, 5)):
             for name, fn in arms:
                 r = fn()
@@ -162,6 +195,8 @@ def main():
                 warm[name].append(r)
             if args.parent:
                 warm["parent_demux_r"].append(demux_r(os.path.abspath(args.parent), csv_path))
+                if args.stats_arm:
+                    warm["parent_one_pass"].append(parent_one_pass(os.path.abspath(args.parent)))
 
         def strip(r):
             return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items() if k not in ("dir", "csv")}
@@ -204,11 +239,27 @@ def main():
                 "report_minus_one_pass_s": round(statistics.median(rep_t) - statistics.median(one_t), 4),
                 "M_pairs_per_s": round(n_pairs / statistics.median(rep_t) / 1e6, 4)})
             doc["report_arm"] = report_doc
+        if stats_doc is not None:
+            sta_t = [r["total_s"] for r in warm["stats"]]
+            stats_doc.update({
+                "what": "demux -b -n 1 --stats CSV (output files and the per-output table in one pass) against demux "
+                        "-b -n 1 on this tree and at the parent commit, in the same alternating rounds",
+                "stats_total_s": spread(sta_t),
+                "one_pass_total_s": spread(one_t),
+                "stats_minus_one_pass_s": round(statistics.median(sta_t) - statistics.median(one_t), 4),
+                # the kernel is queued after the route and waited for with the writers' compression
+                "stages_ms_per_window": {name: {k: per_window_ms([r["stages"] for r in runs], k)
+                                                for k in ("route", "deflate/fetch")}
+                                         for name, runs in (("stats", warm["stats"]), ("one_pass", warm["one_pass"]))}})
+            if warm["parent_one_pass"]:
+                stats_doc["parent_one_pass_total_s"] = spread([r["total_s"] for r in warm["parent_one_pass"]])
+            doc["stats_arm"] = stats_doc
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
             f.write("\n")
-        print(json.dumps({k: doc[k] for k in ("tree_hash", "outputs_equal", "warm", "stages_ms_per_window", "report_arm")
+        print(json.dumps({k: doc[k] for k in ("tree_hash", "outputs_equal", "warm", "stages_ms_per_window", "report_arm",
+                                                   "stats_arm")
                           if k in doc}))
         if not equal:
             raise SystemExit("the two routes' outputs differ: " +
