@@ -282,9 +282,16 @@ __global__ __launch_bounds__(DWG) void dmx_index(const u8* buf, u64 len, u32 nti
     }
 }
 
-__global__ void dmx_first_error(const int32_t* dest, u64 n, unsigned long long* first) {
-    for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
-        if (dest[i] < 0) atomicMin(first, (unsigned long long)i);
+// first[0]: the first record with a negative destination; first[1]: cleared when some destination is >= n_dest
+// (a plain store of one value: no order among the writers is needed)
+__global__ void dmx_first_error(const int32_t* dest, u64 n, int n_dest, unsigned long long* first) {
+    for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const int32_t v = dest[i];
+        if (v < 0)
+            atomicMin(first, (unsigned long long)i);
+        else if (v >= n_dest)
+            first[1] = 0ull;
+    }
 }
 
 __global__ void dmx_keys(const int32_t* dest, u64 n, u32* keys, u32* idx) {
@@ -671,14 +678,15 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     d->hoff[0].assign((size_t)std::max(n_dest, 0) + 1, 0);
     d->hoff[1].assign((size_t)std::max(n_dest, 0) + 1, 0);
     if (!P) return FR_OK;
-    DK(ensure(&d->fe, d->c_fe, 1));
+    DK(ensure(&d->fe, d->c_fe, 2));
     unsigned long long* fe = d->fe;
-    DK(hipMemsetAsync(fe, 0xFF, 8, d->stream));
-    hipLaunchKernelGGL(dmx_first_error, dim3(grid_for(P)), dim3(256), 0, d->stream, d->dest, P, fe);
+    DK(hipMemsetAsync(fe, 0xFF, 16, d->stream));
+    hipLaunchKernelGGL(dmx_first_error, dim3(grid_for(P)), dim3(256), 0, d->stream, d->dest, P, n_dest, fe);
     DK(hipGetLastError());
-    u64 first = 0;
-    DK(hipMemcpyAsync(&first, fe, 8, hipMemcpyDeviceToHost, d->stream));
+    u64 fe_h[2] = {0, 0};  // {first negative destination, 0 when one is >= n_dest}
+    DK(hipMemcpyAsync(fe_h, fe, 16, hipMemcpyDeviceToHost, d->stream));
     DK(hipStreamSynchronize(d->stream));
+    const u64 first = fe_h[0];
     if (first != ~0ull) {
         int32_t v = 0;
         DK(hipMemcpy(&v, d->dest + first, 4, hipMemcpyDeviceToHost));
@@ -686,6 +694,8 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
         *error_val = v;
         return FR_OK;
     }
+    // dmx_bounds indexes first_pos by the destination and the sort looks at its low bits only: refuse, route nothing
+    if (fe_h[1] != ~0ull) return d->err = "fr_dmx_route: destination out of range", FR_ERR_INVALID;
     // stable partition by destination (temporaries cached in the context, grow-only)
     DK(ensure(&d->k_in, d->c_k_in, P));
     DK(ensure(&d->k_out, d->c_k_out, P));

@@ -401,7 +401,9 @@ int fr_dmx_patch(fr_dmx* d, const uint64_t* recs, const int32_t* dest, uint64_t 
 /* route the first n_pairs record pairs: if some pair has a negative destination, *first_error is
  * the first such pair and *error_val its value (nothing routed); otherwise both mates' records
  * are gathered destination-major (record order kept within a destination) and the byte count
- * of every destination is returned per mate */
+ * of every destination is returned per mate.  With no negative destination among them, a destination
+ * >= n_dest is FR_ERR_INVALID ("fr_dmx_route: destination out of range"): nothing is routed, fr_dmx_fetch
+ * has no bytes and no fr_dmx_tally_window / fr_dmx_stats_window is pending */
 int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, int32_t* error_val,
                  uint64_t* bytes_r1, uint64_t* bytes_r2);
 /* the routed bytes of a mate (destination-major) */
