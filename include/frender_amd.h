@@ -45,6 +45,13 @@ extern "C" {
 
 typedef struct fr_ctx fr_ctx;
 
+/* Lines end at "\r\n", '\r' or '\n' (a '\r' that is the data's last byte ends its line: nothing follows it);
+ * a last line without a terminator counts.  A header without ' ' is a record like any other but tallies no
+ * code, and the tally goes on past it: the other headers of the file are counted as usual (the host raises the
+ * reference's error from `error`).  With -s nothing past the last sampled header is tallied or is an error, and
+ * `lines` and `utf8_bad` are those of the bytes the library scanned, which reach at least to the last sampled
+ * header and at most to the file's end (fr_feed_device scans the whole file; fr_feed stops at a line end of its
+ * own choosing once the sample is complete): 4 * records - 3 <= lines <= the file's lines. */
 typedef struct fr_file_stats {
     uint64_t records;        /* header lines counted (after -s), = `actual_reads` (frender.py:160-166) */
     uint64_t lines;          /* lines in the file (universal newlines) */

@@ -71,11 +71,12 @@ class FakeContext:
 
     def end_file(self):
         data = bytes(self.buf)
-        st = types.SimpleNamespace(records=0, new_keys=0, exotic=0, error=0, utf8_bad=0, lines=0)
+        st = types.SimpleNamespace(records=0, new_keys=0, exotic=0, error=0, utf8_bad=0, lines=0, error_offset=0)
         try:
             data.decode("utf-8")
         except UnicodeDecodeError:
             st.utf8_bad = 1
+            st.error = _lib.FR_SCAN_UTF8
         starts, pos, k = [], 0, 0
         for m in LINE.finditer(data):
             if k % 4 == 0:
@@ -84,23 +85,30 @@ class FakeContext:
         if pos < len(data):
             if k % 4 == 0:
                 starts.append((pos, len(data)))
+            k += 1
+        st.lines = k
         if self.sample:
             starts = starts[: self.sample]
         seen = set()
         tag = (self.fi + 1) << 44
         for s, e in starts:
-            line = data[s:e].decode("utf-8", errors="replace")
+            st.records += 1  # every header within the sample is a record, as fr_end_file counts them
+            line = data[s:e].decode("latin-1")  # byte for byte: an exotic code keeps its bytes (fr_get_exotic_table)
             parts = line.split(" ")
             if len(parts) < 2:
+                # the library reports the first such header's file offset and tallies on (the host raises the
+                # reference's IndexError from the stats)
+                if st.error != _lib.FR_SCAN_NO_SPACE:
+                    st.error_offset = self.base + s
                 st.error = _lib.FR_SCAN_NO_SPACE
-                break
+                continue
             code = parts[1].split(":")[-1]
             key = fast_key(code)
             if key is None:
                 key = _lib.encode_wide(code)
             ordv = tag | ((self.base + s) & ~3)  # the library's ordinals: offsets rounded down to 4 B
             if key is None:
-                tab, key = self.exo, code.encode()
+                tab, key = self.exo, code.encode("latin-1")
                 st.exotic += 1
             else:
                 tab = self.tab
@@ -109,7 +117,6 @@ class FakeContext:
             e[1] = min(e[1], ordv)
             e[2][self.fi] = e[2].get(self.fi, 0) + 1
             seen.add(key)
-            st.records += 1
         st.new_keys = len(seen)
         return st
 
