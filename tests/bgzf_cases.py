@@ -5,11 +5,8 @@ GPU encoder must produce for a stream, and the EOF block.
 The expected bytes come from the encoder's host build (tests/native/frd_host.cpp through
 tests/test_deflate_host.py): a slice of at most 64 KiB is, to that build, one final block without
 history -- exactly a BGZF job of fr_defl_run_bgzf."""
-import atexit
 import functools
-import shutil
 import struct
-import tempfile
 import zlib
 from collections import namedtuple
 
@@ -48,13 +45,10 @@ def walk(buf: bytes) -> list:
     return out
 
 
-@functools.lru_cache(maxsize=None)
 def host_lib():
     """The encoder's host build, compiled once per process."""
-    from test_deflate_host import build_host
-    d = tempfile.mkdtemp(prefix="frd_bgzf_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    return build_host(d)
+    from test_deflate_host import host_lib as lib
+    return lib()
 
 
 def member(body: bytes, text: bytes) -> bytes:

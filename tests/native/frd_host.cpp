@@ -225,4 +225,13 @@ uint64_t frd_host_deflate(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t 
     return o;
 }
 
+// the code lengths of one alphabet as the encoder builds them: huff_gather + huff_sort + huff_lengths over
+// freq[0, n) at a length limit (n <= 286; counts below 1 << 23, as a block's are)
+void frd_host_huff(const uint32_t* freq, uint32_t n, uint32_t maxlen, uint8_t* len) {
+    static HuffWork<NLL> hw;
+    huff_gather(freq, n, hw);
+    huff_sort(hw);
+    huff_lengths(hw, n, maxlen, len);
+}
+
 }  // extern "C"

@@ -4,13 +4,19 @@ Every stream must inflate (zlib) to its bytes with their CRC-32; on the demux's 
 be no larger than zlib level 9 makes it (the reference's writers are gzip.open(..., "wb"),
 frender.py:667-676); and it must be the stream the host build of the same algorithm makes
 (tests/native/frd_host.cpp), byte for byte.  The demux end-to-end tests (tests/test_gpu_scan.py) read
-the GPU-written members through Python's gzip."""
+the GPU-written members through Python's gzip.
+
+The edge suite (one test per family of tests/deflate_cases.py) packs a family's streams back to back into
+one run and holds every stream to the host build's bytes; tests/test_deflate_host.py has read those bytes
+symbol by symbol (tests/deflate_anatomy.py) and shown that each family reaches the path it aims at, so
+equality carries that to the kernel.  After every test the encoder's stored fallbacks must be 0."""
 import gzip
 import zlib
 
 import numpy as np
 import pytest
 
+import deflate_cases as C
 from deflate_cases import DEFLATE_BLOCK, edge_cases, routed_fastq
 
 pytestmark = pytest.mark.gpu
@@ -25,9 +31,21 @@ def dfl():
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    from test_deflate_host import build_host
-    return build_host(tmp_path_factory.mktemp("frd"))
+def host():
+    from test_deflate_host import host_lib
+    return host_lib()
+
+
+def _fallbacks(dfl) -> int:
+    from frender_amd import _lib
+    return int(_lib.lib.fr_defl_stored_fallbacks(dfl.h))
+
+
+@pytest.fixture(autouse=True)
+def no_stored_fallbacks(dfl):
+    """No run of any test here stores a block because the kernel's bit accounting did not add up."""
+    yield
+    assert _fallbacks(dfl) == 0
 
 
 def _streams(comp, out):
@@ -131,3 +149,84 @@ def test_demux_writers_gpu_vs_host(tmp_path):
         gpu_total += os.path.getsize(g / fn)
         z9_total += len(gzip.compress(text, 9))
     assert gpu_total <= z9_total, (gpu_total, z9_total)
+
+
+# ---- the edge suite ------------------------------------------------------------------------------------------
+def _run_pack(dfl, streams):
+    """One packed run; every stream must be the host build's, byte for byte, with its length, its CRC-32 and
+    the zlib round trip (an empty stream: no bytes).  Returns the device's streams."""
+    from test_deflate_host import host_stream
+    data, offs = C.pack(streams)
+    comp, crc, out = dfl.compress(data, offs)
+    got = _streams(comp, out)
+    assert sum(int(c) for c in comp) == out.size
+    for s, d in enumerate(streams):
+        if not d:
+            assert comp[s] == 0 and crc[s] == 0, s
+            continue
+        hb, hcrc = host_stream(d)
+        assert int(comp[s]) == len(got[s]), s
+        assert got[s] == hb, f"stream {s} ({len(d)} bytes): {len(got[s])} bytes, the host build {len(hb)}"
+        assert int(crc[s]) == hcrc == zlib.crc32(d), s
+        assert zlib.decompressobj(-15).decompress(got[s]) == d, s
+    assert _fallbacks(dfl) == 0
+    return got
+
+
+def test_family_tails(dfl, host):
+    """A: every length 1..72, around 1024 k and around 65536 k."""
+    _run_pack(dfl, C.family_tails())
+
+
+def test_family_placement(dfl, host):
+    """B: the two contents at every offsets[s] & 15, between a stream that ends with their first bytes and
+    one that continues their last: sixteen runs, the same two streams in each."""
+    first = None
+    for a in range(16):
+        streams, idx = C.placement_pack(a)
+        got = _run_pack(dfl, streams)
+        mine = [got[i] for i in idx]
+        first = first or mine
+        assert mine == first, a
+
+
+def test_family_edges(dfl, host):
+    """C: copies across a sub-range edge and a block edge, and at distances 32767, 32768 and 32769 in the
+    second and the third block."""
+    _run_pack(dfl, list(C.family_edges().values()))
+
+
+def test_family_in_batch(dfl, host):
+    """D: runs of every period at every lane of a batch: the in-batch candidate search."""
+    _run_pack(dfl, C.family_in_batch())
+
+
+def test_family_huffman(dfl, host):
+    """E: the length-limit repair of the lit/len and the code-length code, all 256 values, one value, one
+    distance code, no match, a repeat item across the two length vectors."""
+    _run_pack(dfl, list(C.family_huffman().values()))
+
+
+def test_family_stored(dfl, host):
+    """F: the stored / dynamic choice at its threshold, final and not, and a stored job in mid-stream."""
+    _run_pack(dfl, list(C.family_stored().values()))
+
+
+def test_family_second_job(dfl, host):
+    """G: three jobs per workgroup (the grid is 2 x CUs): a full dynamic block, a 7-byte stream and a
+    stored block on one workgroup in both orders, three streams of in-batch runs on another, 100-byte streams
+    on all others.  Every stream equals the host build's (_run_pack).  The special streams and a few others
+    are also compressed alone on the device and compared: a sample, because a stream alone that equals the
+    host build's is the packed one by the check above, and some 1500 more launches would buy nothing."""
+    try:
+        import torch
+        cus = int(torch.cuda.get_device_properties(0).multi_processor_count)
+    except Exception:
+        cus = 0
+    grid = 2 * (cus if cus > 0 else 512)
+    streams, special = C.second_job_pack(grid)
+    assert len(streams) >= 3 * grid and all(0 < len(s) <= DEFLATE_BLOCK for s in streams)  # one job each
+    got = _run_pack(dfl, streams)
+    for j in special + [0, 1, grid, 2 * grid, len(streams) - 1]:
+        comp, crc, out = dfl.compress(streams[j])
+        assert out.tobytes() == got[j] and int(crc[0]) == zlib.crc32(streams[j]), j
