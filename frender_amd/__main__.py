@@ -93,6 +93,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "quality bytes and their Phred sum, mean quality, %% >= Q30 and %% of the reads; a row pair "
                         "per planned output, samples without reads included; summed on the GPU in the same pass "
                         "(-r and -b)")
+    d.add_argument("--cycle-stats", metavar="cycle_csv",
+                   help="also write a CSV of every output's base composition and quality by cycle (position in the "
+                        "read), per read (R1, R2): A, C, G, T, N and other bases, quality bytes, bases >= Q30, their "
+                        "Phred sum, mean quality and %% >= Q30 at every cycle up to the longest read's, cycles past 512 "
+                        "in one last row; counted on the GPU in the same pass (-r and -b)")
     d.add_argument("--strict-header", action="store_true",
                    help="reject a results file in scan's own column order, as frender.py does (default: accept it)")
     d.add_argument("--gz-level", type=int, default=None,
@@ -141,11 +146,12 @@ def main(argv=None):
         frender_scan(args)
         return 0
     if getattr(args, "cmd", None) == "demux":
-        from .host import demux_mode, gz_format, mismatch_limits, report_args, stats_path
+        from .host import cycle_stats_path, demux_mode, gz_format, mismatch_limits, report_args, stats_path
         try:
             demux_mode(args)  # -r or -b with -n, before ranks start (frender_demux checks it too)
             report_args(args)  # --report with -b, -p with --report
             stats_path(args)  # --stats and --report name two files
+            cycle_stats_path(args)  # --cycle-stats names a third
             mismatch_limits(args)  # --n2 with --single-index
         except SystemExit as e:
             parser.error(str(e))

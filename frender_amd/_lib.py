@@ -174,6 +174,9 @@ _SIGS = {
     "fr_dmx_stats_begin": (C.c_int, [P, C.c_int]),
     "fr_dmx_stats_window": (C.c_int, [P, C.c_uint64]),
     "fr_dmx_stats_get": (C.c_int, [P, C.c_int, P]),
+    "fr_dmx_cycles_begin": (C.c_int, [P, C.c_int, C.c_int]),
+    "fr_dmx_cycles_window": (C.c_int, [P, C.c_uint64]),
+    "fr_dmx_cycles_get": (C.c_int, [P, C.c_int, C.c_int, P]),
     "fr_defl_create": (P, [C.c_int]),
     "fr_defl_destroy": (None, [P]),
     "fr_defl_last_error": (C.c_char_p, [P]),
@@ -631,6 +634,21 @@ class Demux:
         quality_raw_sum)."""
         out = np.zeros((2, max(int(n_dest), 0), 5), np.uint64)
         self._ck(lib.fr_dmx_stats_get(self.h, int(n_dest), _ptr(out)), "fr_dmx_stats_get")
+        return out
+
+    # ---- the windows' per-cycle statistics (demux --cycle-stats; fr_dmx_cycles_*) ----------
+    def cycles_begin(self, n_dest: int, max_cycles: int):
+        self._ck(lib.fr_dmx_cycles_begin(self.h, int(n_dest), int(max_cycles)), "fr_dmx_cycles_begin")
+
+    def cycles_window(self, n_pairs: int):
+        """Add the n_pairs record pairs the last route() routed to the per-destination, per-cycle sums."""
+        self._ck(lib.fr_dmx_cycles_window(self.h, int(n_pairs)), "fr_dmx_cycles_window")
+
+    def cycles_get(self, n_dest: int, max_cycles: int) -> np.ndarray:
+        """uint64 [2, n_dest, max_cycles + 1, 9]: per mate, destination and cycle (the last bin: every cycle at or
+        past max_cycles) the counts of A, C, G, T, N, other, then quality_bytes, q30_bases, quality_raw_sum."""
+        out = np.zeros((2, max(int(n_dest), 0), max(int(max_cycles), 0) + 1, 9), np.uint64)
+        self._ck(lib.fr_dmx_cycles_get(self.h, int(n_dest), int(max_cycles), _ptr(out)), "fr_dmx_cycles_get")
         return out
 
 

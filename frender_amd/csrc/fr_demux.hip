@@ -17,6 +17,8 @@
 // and their tables are fr_dmx_tally.hip's, the entry points at the end of this file check mode and call order.
 // With fr_dmx_stats_begin (`demux --stats`) the routed records are also summed per destination (reads, bases, quality):
 // fr_dmx_stats.hip's kernel over the routed bytes, entered the same way.
+// With fr_dmx_cycles_begin (`demux --cycle-stats`) they are also counted per destination and cycle (bases by value,
+// quality): fr_dmx_cycles.hip's kernel over the same bytes, entered the same way.
 // The host inflates, normalises universal newlines (frender.py:776 reads in text mode), resolves
 // the rare codes outside the fast alphabet, raises the reference's errors, and gzips each
 // destination's bytes into its writer pair.
@@ -418,6 +420,10 @@ struct fr_dmx {
     // that no fr_dmx_stats_window has added yet
     DmxStats* stats = nullptr;
     u64 stats_ok = 0;
+    // the windows' per-cycle statistics (fr_dmx_cycles_begin; fr_dmx_cycles.hip), and the pairs the last fr_dmx_route
+    // routed that no fr_dmx_cycles_window has added yet
+    DmxCycles* cycles = nullptr;
+    u64 cycles_ok = 0;
 };
 
 #define DK(x)                                                                  \
@@ -463,6 +469,7 @@ void fr_dmx_destroy(fr_dmx* d) {
     for (fr_defl* z : d->defl) fr_defl_destroy(z);
     dmx_tally_destroy(d->tally);
     dmx_stats_destroy(d->stats);
+    dmx_cycles_destroy(d->cycles);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
 }
@@ -535,7 +542,7 @@ int fr_dmx_set_sheet2(fr_dmx* d, fr_ctx* ctx, int num_subs1, int num_subs2, cons
 static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_records) {
     d->src[mate] = buf;
     d->len[mate] = len;
-    d->routed_ok = d->stats_ok = 0;
+    d->routed_ok = d->stats_ok = d->cycles_ok = 0;
     const u32 ntiles = (u32)((len + DT - 1) / DT);
     DK(ensure(&d->cnt, d->c_cnt, (u64)ntiles + 1));
     DK(ensure(&d->base, d->c_base, (u64)ntiles + 1));
@@ -672,7 +679,7 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     if (P >= 0xFFFFFFFFull) return d->err = "too many records in one file pair", FR_ERR_CAPACITY;
     *first_error = -1;
     *error_val = 0;
-    d->routed_ok = d->stats_ok = 0;
+    d->routed_ok = d->stats_ok = d->cycles_ok = 0;
     for (int k = 0; k < n_dest; ++k) bytes_r1[k] = bytes_r2[k] = 0;
     d->out_len[0] = d->out_len[1] = 0;
     d->hoff[0].assign((size_t)std::max(n_dest, 0) + 1, 0);
@@ -752,7 +759,7 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     d->out_len[1] = s2;
     d->hoff[0] = h1;
     d->hoff[1] = h2;
-    d->routed_ok = d->stats_ok = P;
+    d->routed_ok = d->stats_ok = d->cycles_ok = P;
     return FR_OK;
 }
 
@@ -832,6 +839,37 @@ int fr_dmx_stats_get(fr_dmx* d, int n_dest, uint64_t* out) {
         return d->err = "fr_dmx_stats_get: n_dest differs from fr_dmx_stats_begin", FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     return dmx_stats_get(d->stats, out, d->err);
+}
+
+// ---- the windows' per-cycle statistics: the call order is checked here, the work is fr_dmx_cycles.hip's
+int fr_dmx_cycles_begin(fr_dmx* d, int n_dest, int max_cycles) {
+    if (!dmx_cycles_args_ok(n_dest, max_cycles))
+        return d->err = "fr_dmx_cycles_begin: n_dest is negative or max_cycles is not in 1..1024", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    DK(hipStreamSynchronize(d->stream));  // an earlier window's sums may still be queued on the old accumulators
+    d->cycles_ok = 0;
+    return dmx_cycles_begin(&d->cycles, d->device, d->stream, n_dest, max_cycles, d->err);
+}
+
+int fr_dmx_cycles_window(fr_dmx* d, uint64_t n_pairs) {
+    if (!d->cycles) return d->err = "fr_dmx_cycles_window: no fr_dmx_cycles_begin", FR_ERR_INVALID;
+    if (n_pairs != d->cycles_ok)
+        return d->err = "fr_dmx_cycles_window: n_pairs differs from the pairs the last fr_dmx_route routed (or they "
+                        "are added already)", FR_ERR_INVALID;
+    if (d->hoff[0].size() > (size_t)dmx_cycles_n_dest(d->cycles) + 1)
+        return d->err = "fr_dmx_cycles_window: the last fr_dmx_route had more destinations than fr_dmx_cycles_begin",
+               FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    d->cycles_ok = 0;
+    return dmx_cycles_window(d->cycles, d->out[0], d->out[1], d->o1, d->l1, d->o2, d->l2, d->k_out, n_pairs, d->err);
+}
+
+int fr_dmx_cycles_get(fr_dmx* d, int n_dest, int max_cycles, uint64_t* out) {
+    if (!d->cycles) return d->err = "fr_dmx_cycles_get: no fr_dmx_cycles_begin", FR_ERR_INVALID;
+    if (n_dest != dmx_cycles_n_dest(d->cycles) || max_cycles != dmx_cycles_max_cycles(d->cycles))
+        return d->err = "fr_dmx_cycles_get: n_dest or max_cycles differs from fr_dmx_cycles_begin", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    return dmx_cycles_get(d->cycles, out, d->err);
 }
 
 // the routed bytes of a mate through its fr_defl: gzip streams (crc32 set) or BGZF member runs

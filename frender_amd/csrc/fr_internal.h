@@ -427,4 +427,17 @@ int dmx_stats_window(DmxStats* t, const u8* out1, const u8* out2, const u64* o1,
                      const u64* l2, const u32* dest, u64 n, std::string& err);
 int dmx_stats_get(DmxStats* t, u64* out, std::string& err);
 
+// ---- the demux windows' per-cycle statistics (fr_dmx_cycles.hip; fr_demux.hip's fr_dmx_cycles_* entry points check
+// the call order and forward here, as for the statistics above).  acc[2][n_dest][max_cycles + 1][9] u64 in HBM, owned
+// by DmxCycles.  The window's arguments are dmx_stats_window's.
+struct DmxCycles;
+bool dmx_cycles_args_ok(int n_dest, int max_cycles);  // n_dest >= 0 and 1 <= max_cycles <= 1024
+int dmx_cycles_begin(DmxCycles** t, int device, hipStream_t stream, int n_dest, int max_cycles, std::string& err);
+void dmx_cycles_destroy(DmxCycles* t);
+int dmx_cycles_n_dest(const DmxCycles* t);
+int dmx_cycles_max_cycles(const DmxCycles* t);
+int dmx_cycles_window(DmxCycles* t, const u8* out1, const u8* out2, const u64* o1, const u64* l1, const u64* o2,
+                      const u64* l2, const u32* dest, u64 n, std::string& err);
+int dmx_cycles_get(DmxCycles* t, u64* out, std::string& err);
+
 }  // namespace fr

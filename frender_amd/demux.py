@@ -14,6 +14,9 @@ pass also counts every distinct code (fr_dmx_tally_*, Report below) and writes s
 
 `--stats PATH` (both modes): the same pass sums what every output got, per mate -- reads, bases, quality bytes,
 bases >= Q30 and the quality sum -- over the routed records on the GPU (fr_dmx_stats_*, Stats below).
+
+`--cycle-stats PATH` (both modes): the same pass counts, per output, mate and cycle (position in the read), the bases
+by value and the quality bytes, those >= Q30 and their sum (fr_dmx_cycles_*, CycleStats below).
 """
 from __future__ import annotations
 
@@ -33,8 +36,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import (demux_mode, get_indexes, gz_format, input_spec, limits_of, mismatch_limits, num_subs_of,
-                   parse_files, report_args, single_index, stats_path)
+from .host import (cycle_stats_path, demux_mode, get_indexes, gz_format, input_spec, limits_of, mismatch_limits,
+                   num_subs_of, parse_files, report_args, single_index, stats_path)
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
 # the column order `scan` itself writes (frender.py:482-501, report_analysis)
@@ -712,14 +715,99 @@ class Stats:
         self.write(self.path, names, self.sum_ranks([g.view(np.uint64).reshape(shape) for g in got]))
 
 
+MAX_CYCLES = 512  # --cycle-stats: cycles with a row of their own; the cycles past them share the last row
+CYCLE_HEADER = ["output", "read", "cycle", "bases", "A", "C", "G", "T", "N", "other", "quality_bytes", "q30_bases",
+                "quality_sum", "mean_quality", "pct_q30"]
+CYCLE_FIELDS = ("A", "C", "G", "T", "N", "other", "quality_bytes", "q30_bases", "quality_raw_sum")  # fr_dmx_cycles_get's
+
+
+class CycleStats:
+    """`demux --cycle-stats PATH`: where in the read an output is good or bad.  The GPU counts the records of every
+    routed window per destination and cycle (Demux.cycles_*: fr_dmx_cycles.hip; a record and its lines are Stats')
+    and this object turns the counts into the CSV: per planned destination, in plan_destinations' order, and mate
+    the rows of cycles 1..C, C being the last cycle at which any output of that mate has a count, then one row for
+    all cycles past max_cycles if any output has one."""
+
+    def __init__(self, path=None, max_cycles: int = MAX_CYCLES):
+        self.path = None if path is None else str(path)
+        self.max_cycles = int(max_cycles)
+        self.n_dest = 0
+
+    def begin(self, dmx, n_dest: int):
+        self.n_dest = int(n_dest)
+        dmx.cycles_begin(self.n_dest, self.max_cycles)
+
+    def window(self, dmx, n_pairs: int):
+        """The window's first n_pairs records are routed, and still resident: add them."""
+        dmx.cycles_window(n_pairs)
+
+    def local(self, dmx) -> np.ndarray:
+        """This process's counts once its last pair is done: uint64 [2, n_dest, max_cycles + 1, 9] in CYCLE_FIELDS'
+        order."""
+        return dmx.cycles_get(self.n_dest, self.max_cycles)
+
+    @staticmethod
+    def sum_ranks(arrays) -> np.ndarray:
+        """The counts of several ranks as one: [2, n_dest, max_cycles + 1, 9]."""
+        return np.sum([np.asarray(a, dtype=np.uint64) for a in arrays], axis=0, dtype=np.uint64)
+
+    @staticmethod
+    def rows(names, array) -> list:
+        """The CSV's rows without the header; array [2, len(names), max_cycles + 1, 9].  quality_sum =
+        quality_raw_sum - 33 * quality_bytes (Phred+33; it is negative when the bytes are below '!'); a derived column
+        whose denominator is 0 is left empty."""
+        a = np.asarray(array)
+        assert a.ndim == 4 and a.shape[:2] == (2, len(names)) and a.shape[3] == len(CYCLE_FIELDS) and a.shape[2] >= 2, \
+            "cycle stats: the array is not [2, destinations, max_cycles + 1, 9]"
+        mc = a.shape[2] - 1
+
+        def ratio(num, den, scale=1):
+            return f"{scale * num / den:.2f}" if den else ""
+
+        # per mate: the cycles with a row (the table is rectangular per mate), and whether the tail has one
+        used = [np.nonzero(a[m, :, :mc].any(axis=(0, 2)))[0] for m in (0, 1)]
+        last = [int(u[-1]) + 1 if u.size else 0 for u in used]
+        tail = [bool(a[m, :, mc].any()) for m in (0, 1)]
+        out = []
+        for k, name in enumerate(names):
+            for m, read in enumerate(("R1", "R2")):
+                bins = [(c, str(c + 1)) for c in range(last[m])] + ([(mc, f"{mc + 1}+")] if tail[m] else [])
+                for c, label in bins:
+                    v = [int(x) for x in a[m, k, c]]
+                    qbytes, q30, raw = v[6:]
+                    qsum = raw - 33 * qbytes
+                    out.append([name, read, label, sum(v[:6]), *v[:6], qbytes, q30, qsum, ratio(qsum, qbytes),
+                                ratio(q30, qbytes, 100)])
+        return out
+
+    def write(self, path, names, array):
+        with open(path, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(CYCLE_HEADER)
+            w.writerows(self.rows(names, array))
+
+    def write_ranks(self, group, wire, array, names):
+        """`--gpus N`, no rank failed: every rank's counts go to rank 0, which adds them and writes the file."""
+        import torch
+
+        from .dist import gather_rows
+        nf = len(CYCLE_FIELDS)
+        got = gather_rows(group, wire, torch.from_numpy(np.ascontiguousarray(array).view(np.int64).reshape(-1, nf)))
+        if group.get_rank() != 0:
+            return
+        shape = (2, len(names), self.max_cycles + 1, nf)
+        self.write(self.path, names, self.sum_ranks([g.view(np.uint64).reshape(shape) for g in got]))
+
+
 def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of, writers, window, sheet=None,
-                hit=None, report=None, stats=None):
+                hit=None, report=None, stats=None, cycles=None):
     """One R1/R2 pair in record-aligned windows: the GPU indexes both windows, the complete
     record pairs are routed, and the bytes after the last routed record carry into the next
     window.  Pairing stops when either mate runs out of records (zip, frender.py:777).  The mates
     inflate on the native pool gz (files i1, i2).  sheet (SheetMode): `demux -b`, no results; hit: a set
     that collects the destinations pairs were routed to; report (Report, after its begin_pair): `--report`, every
-    routed window is counted; stats (Stats, after its begin): `--stats`, every routed window is summed."""
+    routed window is counted; stats (Stats, after its begin): `--stats`, every routed window is summed; cycles
+    (CycleStats, after its begin): `--cycle-stats`, every routed window is counted per cycle."""
     streams =[text_chunks(read1_file, gz, i1), text_chunks(read2_file, gz, i2)]
     bufs = [[], []]  # each mate's window as a list of decoded blocks (never joined on the host)
     eof = [False, False]
@@ -772,6 +860,8 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 report.window(dmx, n_pairs, ex, codes)
             if stats is not None:  # queued behind the route, on the bytes it gathered
                 stats.window(dmx, n_pairs)
+            if cycles is not None:  # the same, per cycle
+                cycles.window(dmx, n_pairs)
             if hit is not None:
                 hit.update(np.nonzero(b1 + b2)[0].tolist())
             # each mate's bytes for the files and their per-destination sizes, as the writers' family makes them
@@ -880,6 +970,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     mode = demux_mode(args)
     report_path, prefix = report_args(args)
     stats_file = stats_path(args)
+    cycles_file = cycle_stats_path(args)
     fmt = gz_format(args)
     single = single_index(args)
     num_subs = num_subs_of(*mismatch_limits(args)) if mode == "b" else None  # --n2 with --single-index: refused here
@@ -920,6 +1011,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     hit = set()
     report = Report(report_path, prefix) if report_path is not None else None  # --report (with -b: report_args)
     stats = Stats(stats_file) if stats_file is not None else None  # --stats
+    cycles = CycleStats(cycles_file) if cycles_file is not None else None  # --cycle-stats
 
     table = None
     if mode == "r":
@@ -932,7 +1024,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     window = int(getattr(args, "window", None) or (512 << 20))  # decoded bytes per mate per GPU pass
     if group is not None:
         return _demux_ranks(group, args, pairs, results, route_of, table, writers, window, level, infix, kind, sheet,
-                            lazy, t_start, report, stats)
+                            lazy, t_start, report, stats, cycles)
     paths = [str(f) for pr in pairs for f in pr]
     try:
         with _session(t_start, paths, kind, len(writers), _device_index(None), sheet, table, dev, ctx,
@@ -941,12 +1033,14 @@ def frender_demux(args, dev=None, ctx=None) -> None:
                 report.begin(dmx)
             if stats is not None:
                 stats.begin(dmx, len(names))
+            if cycles is not None:
+                cycles.begin(dmx, len(names))
             for k, (read1_file, read2_file) in enumerate(pairs):
                 print(f"Demultiplexing {read1_file.name}...")
                 if report is not None:
                     report.begin_pair(dmx, k)
                 _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers,
-                            window, sheet, hit, report, stats)
+                            window, sheet, hit, report, stats, cycles)
             if sheet is not None and samples and not (hit & lazy):
                 print(NO_SAMPLES_WARNING)  # known only now: no pair was demuxable
             if report is not None:  # every pair is routed: the table is complete
@@ -954,6 +1048,9 @@ def frender_demux(args, dev=None, ctx=None) -> None:
             if stats is not None:
                 print(f"Writing demux statistics to {stats.path}")
                 stats.write(stats.path, names, stats.local(dmx))
+            if cycles is not None:
+                print(f"Writing demux cycle statistics to {cycles.path}")
+                cycles.write(cycles.path, names, cycles.local(dmx))
     finally:
         STAGE_TIMES["total"] = time.perf_counter() - t_start
         if getattr(args, "stage_times", False):
@@ -1010,7 +1107,7 @@ def _mkdir_everywhere(group, path):
 
 
 def _demux_ranks(group, args, pairs, results, route_of, table, names, window, level, infix, kind, sheet, lazy,
-                 t_start, report=None, stats=None):
+                 t_start, report=None, stats=None, cycles=None):
     import shutil
 
     from .dist import PeerFailed, reduce_min
@@ -1020,6 +1117,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
     failed, exc = len(pairs), None
     tally = None  # --report: this rank's table, once its last pair is done
     sums = None  # --stats: this rank's sums, once its last pair is done
+    counts = None  # --cycle-stats: this rank's counts, once its last pair is done
     try:
         # the session opens inside the try: a rank whose pool or device fails still joins the collectives below
         # (-b: this rank's own sheet context: classification is stateless, nothing is exchanged)
@@ -1029,6 +1127,8 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                 report.begin(dmx)
             if stats is not None:
                 stats.begin(dmx, len(names))
+            if cycles is not None:
+                cycles.begin(dmx, len(names))
             for j, k in enumerate(mine):
                 d = os.path.join(parts, str(k))
                 os.makedirs(d, exist_ok=True)
@@ -1038,7 +1138,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                     if report is not None:
                         report.begin_pair(dmx, k)  # the global pair index: the ordinals are the one-process run's
                     _demux_pair(dmx, pool, gz, 2 * j, 2 * j + 1, pairs[k][0], pairs[k][1], results, route_of, writers,
-                                window, sheet, hit, report, stats)
+                                window, sheet, hit, report, stats, cycles)
                 except (Exception, SystemExit) as e:  # re-raised below if it is the first in pair order
                     failed, exc = k, e
                 finally:
@@ -1049,6 +1149,8 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                 tally = report.local(dmx)
             if stats is not None and exc is None:
                 sums = stats.local(dmx)
+            if cycles is not None and exc is None:
+                counts = cycles.local(dmx)
     except (Exception, SystemExit) as e:  # before any pair (the device, the table): this rank's first pair
         if exc is None:
             failed, exc = (mine[0] if mine else len(pairs)), e
@@ -1092,3 +1194,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
         if rank == 0:
             print(f"Writing demux statistics to {stats.path}")
         stats.write_ranks(group, _wire(group), sums, names)
+    if cycles is not None:  # after --stats' line
+        if rank == 0:
+            print(f"Writing demux cycle statistics to {cycles.path}")
+        cycles.write_ranks(group, _wire(group), counts, names)

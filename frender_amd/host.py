@@ -215,6 +215,21 @@ def stats_path(args):
     return path
 
 
+def cycle_stats_path(args):
+    """--cycle-stats PATH of a demux's arguments, or None (a namespace without the field has no per-cycle
+    statistics).  It cannot be --report's file or --stats' file.  Called with stats_path, before anything is opened
+    or created."""
+    path = getattr(args, "cycle_stats", None)
+    if path is None:
+        return None
+    here = os.path.abspath(os.fspath(path))
+    for flag, other in (("--report", getattr(args, "report", None)), ("--stats", getattr(args, "stats", None))):
+        if other is not None and os.path.abspath(os.fspath(other)) == here:
+            raise SystemExit(f"demux --cycle-stats: the per-cycle statistics and {flag} cannot be written to the same "
+                             "file")
+    return path
+
+
 def gz_format(args) -> str:
     """--gz-format of a demux's arguments (a namespace without it means gzip), checked against --gz-writer:
     only the GPU writer makes BGZF.  Called before anything is opened or created."""

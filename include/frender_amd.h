@@ -410,7 +410,7 @@ int fr_dmx_patch(fr_dmx* d, const uint64_t* recs, const int32_t* dest, uint64_t 
  * are gathered destination-major (record order kept within a destination) and the byte count
  * of every destination is returned per mate.  With no negative destination among them, a destination
  * >= n_dest is FR_ERR_INVALID ("fr_dmx_route: destination out of range"): nothing is routed, fr_dmx_fetch
- * has no bytes and no fr_dmx_tally_window / fr_dmx_stats_window is pending */
+ * has no bytes and no fr_dmx_tally_window / fr_dmx_stats_window / fr_dmx_cycles_window is pending */
 int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, int32_t* error_val,
                  uint64_t* bytes_r1, uint64_t* bytes_r2);
 /* the routed bytes of a mate (destination-major) */
@@ -481,6 +481,27 @@ int fr_dmx_stats_window(fr_dmx* d, uint64_t n_pairs);
 /* out[2][n_dest][5]: per mate and destination {reads, bases, quality_bytes, q30_bases, quality_raw_sum}; n_dest
  * as begun.  Synchronises. */
 int fr_dmx_stats_get(fr_dmx* d, int n_dest, uint64_t* out);
+
+/* ---- the demux windows' per-cycle statistics (`demux --cycle-stats`; fr_dmx_cycles.hip): where in the read an
+ * output is good or bad, per mate, destination and 0-based cycle c, summed over the routed records while they are
+ * resident: table mode and sheet mode alike.  A record and its lines are fr_dmx_stats_*'s.  Per record, for every
+ * c < len(sequence line) one of six counters gets +1 by the byte's exact value: A, C, G, T, N, other (every other
+ * value: lower case and bytes >= 0x80 included); for every c < len(quality line) quality_bytes += 1, q30_bases +=
+ * (byte >= 63, unsigned) and quality_raw_sum += byte.  The two lengths are independent.  Cycles at or past
+ * max_cycles share one tail bin, index max_cycles.  Summed over the bins, the six base counters are
+ * fr_dmx_stats_get's bases, and the three quality fields its own.  Every call below returns FR_ERR_INVALID, with
+ * the sums untouched, when the order described is not kept. */
+/* Start (or clear) the per-cycle statistics of a demux: n_dest destinations, max_cycles bins and the tail, all sums
+ * zero.  Off, and nothing allocated, until this call.  1 <= max_cycles <= 1024, n_dest >= 0. */
+int fr_dmx_cycles_begin(fr_dmx* d, int n_dest, int max_cycles);
+/* Add the n_pairs record pairs the last fr_dmx_route routed (it found no negative destination; n_pairs must be
+ * its count; a window is added once; before the next fr_dmx_load*; that route's n_dest is at most the begun
+ * one).  Independent of fr_dmx_tally_window and fr_dmx_stats_window: each may follow one route, once.  Queues on
+ * the context's stream and makes no synchronisation of its own. */
+int fr_dmx_cycles_window(fr_dmx* d, uint64_t n_pairs);
+/* out[2][n_dest][max_cycles + 1][9]: per mate, destination and bin {A, C, G, T, N, other, quality_bytes,
+ * q30_bases, quality_raw_sum}; n_dest and max_cycles as begun.  Synchronises. */
+int fr_dmx_cycles_get(fr_dmx* d, int n_dest, int max_cycles, uint64_t* out);
 
 /* ---- GPU deflate over any byte ranges (fr_deflate.hip; fr_dmx_deflate runs it on the routed bytes).
  * Stream s is bytes [offsets[s], offsets[s + 1]) of the device buffer dev_data (4-byte aligned, 16

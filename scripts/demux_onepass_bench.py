@@ -17,8 +17,10 @@ from the same alternating rounds.  With --report-arm, `demux -b --report` joins 
 scan + demux -r, so that is its comparison, and its CSV is compared with the scan's (the first runs').  With
 --stats-arm, `demux -b --stats` joins the rounds: its comparison is `demux -b` without the flag on this tree (the
 flag's cost is the difference) and, with --parent, the parent's `demux -b`, which this tree's must equal without the
-flag; its output files are compared with the one-pass run's.  Writes one JSON document (--out), stamped with the
-tree's source hash.
+flag; its output files are compared with the one-pass run's.  With --cycle-stats-arm, `demux -b --cycle-stats` joins
+the rounds in the same way: the flag's cost is its difference to `demux -b` on this tree, and with --parent the
+parent's `demux -b` is timed in the same rounds, which this tree's must equal without the flag.  Writes one JSON
+document (--out), stamped with the tree's source hash.
 
 Needs a GPU: there is no CPU path to time.
 """
@@ -88,6 +90,9 @@ def main():
     ap.add_argument("--stats-arm", action="store_true", help="also time demux -b --stats (the per-output table from "
                                                               "the same pass) and, with --parent, the parent's demux "
                                                               "-b in the same rounds")
+    ap.add_argument("--cycle-stats-arm", action="store_true",
+                    help="also time demux -b --cycle-stats (the per-cycle table from the same pass) and, with "
+                         "--parent, the parent's demux -b in the same rounds")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "demux_sheet_bench.json"))
     ap.add_argument("--workdir", help="where the inputs and outputs go (default: a temporary directory)")
     args = ap.parse_args()
@@ -146,6 +151,14 @@ def main():
                          os.path.join(w, "out"), "--stage-times", *allf], w, ROOT)
             return {"total_s": t, "stages": st, "dir": w, "csv": os.path.join(w, "stats.csv")}
 
+        def cycles_pass():
+            serial[0] += 1
+            w = os.path.join(d, f"cyc_{serial[0]}")
+            os.mkdir(w)
+            t, st = run(["demux", "-b", sheet_csv, "-n", "1", "--cycle-stats", os.path.join(w, "cycles.csv"), "-d",
+                         os.path.join(w, "out"), "--stage-times", *allf], w, ROOT)
+            return {"total_s": t, "stages": st, "dir": w, "csv": os.path.join(w, "cycles.csv")}
+
         def parent_one_pass(root):
             serial[0] += 1
             w = os.path.join(d, f"pone_{serial[0]}")
@@ -180,14 +193,25 @@ def main():
             stats_doc = {"outputs_equal": digests(os.path.join(cold["stats"]["dir"], "out")) == db,
                          "csv_rows": len(rows),
                          "csv_reads": {m: sum(int(r["reads"]) for r in rows if r["read"] == m) for m in ("R1", "R2")}}
+        cycles_doc = None
+        if args.cycle_stats_arm:
+            cold["cycles"] = cycles_pass()
+            with open(cold["cycles"]["csv"], newline="") as f:
+                rows = list(csv.DictReader(f))
+            cycles_doc = {"outputs_equal": digests(os.path.join(cold["cycles"]["dir"], "out")) == db,
+                          "csv_rows": len(rows), "csv_bytes": os.path.getsize(cold["cycles"]["csv"]),
+                          "csv_cycles": {m: len({r["cycle"] for r in rows if r["read"] == m}) for m in ("R1", "R2")},
+                          "csv_bases": {m: sum(int(r["bases"]) for r in rows if r["read"] == m) for m in ("R1", "R2")}}
         csv_path = os.path.join(d, "results.csv")
         shutil.copy(cold["two_pass"]["csv"], csv_path)
         out_files = len(da)
         for c in cold.values():
             shutil.rmtree(c["dir"])
-        warm = {"two_pass": [], "one_pass": [], "report": [], "stats": [], "parent_demux_r": [], "parent_one_pass": []}
+        warm = {"two_pass": [], "one_pass": [], "report": [], "stats": [], "cycles": [], "parent_demux_r": [],
+                "parent_one_pass": []}
         arms = (("two_pass", two_pass), ("one_pass", one_pass)) + ((("report", report_pass),) if args.report_arm else ()) \
-            + ((("stats", stats_pass),) if args.stats_arm else ())
+            + ((("stats", stats_pass),) if args.stats_arm else ()) \
+            + ((("cycles", cycles_pass),) if args.cycle_stats_arm else ())
         for _ in range(max(args.runs, 5)):
             for name, fn in arms:
                 r = fn()
@@ -195,7 +219,7 @@ def main():
                 warm[name].append(r)
             if args.parent:
                 warm["parent_demux_r"].append(demux_r(os.path.abspath(args.parent), csv_path))
-                if args.stats_arm:
+                if args.stats_arm or args.cycle_stats_arm:
                     warm["parent_one_pass"].append(parent_one_pass(os.path.abspath(args.parent)))
 
         def strip(r):
@@ -254,12 +278,27 @@ def main():
             if warm["parent_one_pass"]:
                 stats_doc["parent_one_pass_total_s"] = spread([r["total_s"] for r in warm["parent_one_pass"]])
             doc["stats_arm"] = stats_doc
+        if cycles_doc is not None:
+            cyc_t = [r["total_s"] for r in warm["cycles"]]
+            cycles_doc.update({
+                "what": "demux -b -n 1 --cycle-stats CSV (output files and the per-cycle table in one pass) against "
+                        "demux -b -n 1 on this tree and at the parent commit, in the same alternating rounds",
+                "cycles_total_s": spread(cyc_t),
+                "one_pass_total_s": spread(one_t),
+                "cycles_minus_one_pass_s": round(statistics.median(cyc_t) - statistics.median(one_t), 4),
+                # the kernel is queued after the route and waited for with the writers' compression
+                "stages_ms_per_window": {name: {k: per_window_ms([r["stages"] for r in runs], k)
+                                                for k in ("route", "deflate/fetch")}
+                                         for name, runs in (("cycles", warm["cycles"]), ("one_pass", warm["one_pass"]))}})
+            if warm["parent_one_pass"]:
+                cycles_doc["parent_one_pass_total_s"] = spread([r["total_s"] for r in warm["parent_one_pass"]])
+            doc["cycle_stats_arm"] = cycles_doc
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
             f.write("\n")
         print(json.dumps({k: doc[k] for k in ("tree_hash", "outputs_equal", "warm", "stages_ms_per_window", "report_arm",
-                                                   "stats_arm")
+                                                   "stats_arm", "cycle_stats_arm")
                           if k in doc}))
         if not equal:
             raise SystemExit("the two routes' outputs differ: " +
