@@ -98,6 +98,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "read), per read (R1, R2): A, C, G, T, N and other bases, quality bytes, bases >= Q30, their "
                         "Phred sum, mean quality and %% >= Q30 at every cycle up to the longest read's, cycles past 512 "
                         "in one last row; counted on the GPU in the same pass (-r and -b)")
+    d.add_argument("--barcode-stats", metavar="barcode_csv",
+                   help="with -b: also write a CSV of how well the barcodes matched: per planned output, the reads by "
+                        "mismatches in index 1 and in index 2 (0, 1, 2, 3+ or none) against the sheet row the read was "
+                        "assigned to (demuxable) or the first row each index matches (index hop, ambiguous); counted "
+                        "on the GPU in the same pass")
     d.add_argument("--strict-header", action="store_true",
                    help="reject a results file in scan's own column order, as frender.py does (default: accept it)")
     d.add_argument("--gz-level", type=int, default=None,
@@ -146,12 +151,14 @@ def main(argv=None):
         frender_scan(args)
         return 0
     if getattr(args, "cmd", None) == "demux":
-        from .host import cycle_stats_path, demux_mode, gz_format, mismatch_limits, report_args, stats_path
+        from .host import (barcode_stats_path, cycle_stats_path, demux_mode, gz_format, mismatch_limits, report_args,
+                           stats_path)
         try:
             demux_mode(args)  # -r or -b with -n, before ranks start (frender_demux checks it too)
             report_args(args)  # --report with -b, -p with --report
             stats_path(args)  # --stats and --report name two files
             cycle_stats_path(args)  # --cycle-stats names a third
+            barcode_stats_path(args)  # --barcode-stats with -b, and a fourth file
             mismatch_limits(args)  # --n2 with --single-index
         except SystemExit as e:
             parser.error(str(e))

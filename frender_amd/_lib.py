@@ -177,6 +177,10 @@ _SIGS = {
     "fr_dmx_cycles_begin": (C.c_int, [P, C.c_int, C.c_int]),
     "fr_dmx_cycles_window": (C.c_int, [P, C.c_uint64]),
     "fr_dmx_cycles_get": (C.c_int, [P, C.c_int, C.c_int, P]),
+    "fr_dmx_bstats_begin": (C.c_int, [P, C.c_int]),
+    "fr_dmx_bstats_patch": (C.c_int, [P, P, P, C.c_uint64]),
+    "fr_dmx_bstats_window": (C.c_int, [P, C.c_uint64]),
+    "fr_dmx_bstats_get": (C.c_int, [P, C.c_int, P]),
     "fr_defl_create": (P, [C.c_int]),
     "fr_defl_destroy": (None, [P]),
     "fr_defl_last_error": (C.c_char_p, [P]),
@@ -649,6 +653,28 @@ class Demux:
         past max_cycles) the counts of A, C, G, T, N, other, then quality_bytes, q30_bases, quality_raw_sum."""
         out = np.zeros((2, max(int(n_dest), 0), max(int(max_cycles), 0) + 1, 9), np.uint64)
         self._ck(lib.fr_dmx_cycles_get(self.h, int(n_dest), int(max_cycles), _ptr(out)), "fr_dmx_cycles_get")
+        return out
+
+    # ---- the windows' index mismatch table (demux -b --barcode-stats; fr_dmx_bstats_*) -----
+    def bstats_begin(self, n_dest: int):
+        self._ck(lib.fr_dmx_bstats_begin(self.h, int(n_dest)), "fr_dmx_bstats_begin")
+
+    def bstats_patch(self, recs, bins):
+        """The bin bytes (bin1 * 5 + bin2) of the R2 records the host resolved, beside patch()."""
+        r = np.ascontiguousarray(recs, dtype=np.uint64)
+        b = np.ascontiguousarray(bins, dtype=np.uint8)
+        if r.size != b.size:
+            raise ValueError("bstats_patch: one bin byte per record")
+        self._ck(lib.fr_dmx_bstats_patch(self.h, _ptr(r), _ptr(b), r.size), "fr_dmx_bstats_patch")
+
+    def bstats_window(self, n_pairs: int):
+        """Count the n_pairs record pairs the last route() routed per destination and bin pair."""
+        self._ck(lib.fr_dmx_bstats_window(self.h, int(n_pairs)), "fr_dmx_bstats_window")
+
+    def bstats_get(self, n_dest: int) -> np.ndarray:
+        """uint64 [n_dest, 5, 5]: per destination, index-1 bin and index-2 bin (0, 1, 2, 3+, none) the pairs."""
+        out = np.zeros((max(int(n_dest), 0), 5, 5), np.uint64)
+        self._ck(lib.fr_dmx_bstats_get(self.h, int(n_dest), _ptr(out)), "fr_dmx_bstats_get")
         return out
 
 

@@ -433,16 +433,37 @@ hipError_t launch_classify(const u64* keys, const u64* counts, u64 n, SheetArgs 
 // demux key mode (fr_dmx_set_sheet): one lane per R2 record of a window, classified from its fast key as
 // classify_kernel classifies a unique code without rc, and turned into the record's destination at once.
 // No LDS: a sheet of any size takes the same path and registers alone bound the occupancy.
+//
+// EMIT (fr_dmx_bstats_begin, `demux -b --barcode-stats`): the record's mismatch bins go to rec_bin[u] as well, one
+// byte bin1 * 5 + bin2 (bins 0, 1, 2, 3 = three or more, 4 = none).  The reference row of either index comes from
+// the PairClass at hand: the assigned row of a demuxable code, the first matching row of each list (m1, m2) of a
+// hop or an ambiguous code, none of an undetermined one (class_rule leaves m1 = m2 = -1 there); a single-index
+// sheet has no index 2.  The map path may name another row of equal value: the distance is the same.  A record
+// this kernel skips or fails gets DMX_NO_BIN.  Without EMIT the kernel is the one it was, argument block included:
+// rec_bin is a pack of one pointer with EMIT and of nothing without it.
 // ------------------------------------------------------------------------------------
 template <typename W>
+__device__ __forceinline__ u32 mism_bin(W q, const u64* __restrict__ rows, int row) {
+    return row < 0 ? 4u : (u32)min(mism_w<W>(q, (W)rows[row]), 3);
+}
+
+template <typename W, bool EMIT, typename... Bin>
 __global__ __launch_bounds__(CLS_WG) void dmx_class_kernel(const u64* __restrict__ rec_key, int32_t* rec_dest, u64 n,
                                                            SheetArgs sh, int nsubs1, int nsubs2, NbrMap nm,
-                                                           const int32_t* __restrict__ row_dest, DmxClassDest cd) {
+                                                           const int32_t* __restrict__ row_dest, DmxClassDest cd,
+                                                           Bin... bin_out) {
+    static_assert(sizeof...(Bin) == (EMIT ? 1 : 0), "one u8* with EMIT, nothing without");
+    [[maybe_unused]] u8* rec_bin = nullptr;
+    if constexpr (EMIT) rec_bin = (bin_out, ...);
     for (u64 u = blockIdx.x * (u64)CLS_WG + threadIdx.x; u < n; u += (u64)gridDim.x * CLS_WG) {
-        if (rec_dest[u] != DMX_PENDING) continue;  // exotic: the host resolves it
+        if (rec_dest[u] != DMX_PENDING) {  // exotic: the host resolves it
+            if constexpr (EMIT) rec_bin[u] = DMX_NO_BIN;
+            continue;
+        }
         int n1 = 0, n2 = 0;
         u64 q1 = 0, q2 = 0;
         int32_t d;
+        u32 bin = DMX_NO_BIN;
         if (!split_fast_key(rec_key[u], sh.single != 0, n1, n2, q1, q2)) {
             d = FR_DMX_NOPLUS;
         } else if (const int err = length_error(sh, n1, n2)) {
@@ -453,21 +474,29 @@ __global__ __launch_bounds__(CLS_WG) void dmx_class_kernel(const u64* __restrict
                 : c.cls == CLS_HOP   ? cd.v[CLS_HOP]
                 : c.cls == CLS_AMBIG ? cd.v[CLS_AMBIG]
                                      : cd.v[CLS_UNDET];
+            if constexpr (EMIT) {
+                const bool dm = c.cls == CLS_DEMUX;
+                const u32 b1 = mism_bin<W>((W)q1, sh.i1, dm ? c.row : c.m1);
+                const u32 b2 = sh.single ? 4u : mism_bin<W>((W)q2, sh.i2, dm ? c.row : c.m2);
+                bin = b1 * 5u + b2;
+            }
         }
         rec_dest[u] = d;
+        if constexpr (EMIT) rec_bin[u] = (u8)bin;
     }
 }
 
 hipError_t launch_dmx_classify(const u64* rec_key, int32_t* rec_dest, u64 n, SheetArgs sh, int nsubs1, int nsubs2,
-                               const NbrMap& nm, const int32_t* row_dest, DmxClassDest cd, hipStream_t s) {
+                               const NbrMap& nm, const int32_t* row_dest, DmxClassDest cd, u8* rec_bin, hipStream_t s) {
     if (!n) return hipSuccess;
     const u64 grid = std::max<u64>(1, std::min<u64>((n + CLS_WG - 1) / CLS_WG, 2048));
-    if (sheet_is_narrow(sh))
-        hipLaunchKernelGGL(dmx_class_kernel<u32>, dim3((u32)grid), dim3(CLS_WG), 0, s, rec_key, rec_dest, n, sh, nsubs1,
-                           nsubs2, nm, row_dest, cd);
-    else
-        hipLaunchKernelGGL(dmx_class_kernel<u64>, dim3((u32)grid), dim3(CLS_WG), 0, s, rec_key, rec_dest, n, sh, nsubs1,
-                           nsubs2, nm, row_dest, cd);
+    const bool narrow = sheet_is_narrow(sh);
+    auto go = [&](auto kernel, auto... bin_out) {
+        hipLaunchKernelGGL(kernel, dim3((u32)grid), dim3(CLS_WG), 0, s, rec_key, rec_dest, n, sh, nsubs1, nsubs2, nm,
+                           row_dest, cd, bin_out...);
+    };
+    if (rec_bin) narrow ? go(dmx_class_kernel<u32, true, u8*>, rec_bin) : go(dmx_class_kernel<u64, true, u8*>, rec_bin);
+    else narrow ? go(dmx_class_kernel<u32, false>) : go(dmx_class_kernel<u64, false>);
     return hipGetLastError();
 }
 

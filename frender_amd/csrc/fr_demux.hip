@@ -19,6 +19,9 @@
 // fr_dmx_stats.hip's kernel over the routed bytes, entered the same way.
 // With fr_dmx_cycles_begin (`demux --cycle-stats`) they are also counted per destination and cycle (bases by value,
 // quality): fr_dmx_cycles.hip's kernel over the same bytes, entered the same way.
+// With fr_dmx_bstats_begin (sheet mode, `demux -b --barcode-stats`) the classifier also leaves every record's index
+// mismatch bins, and the routed records' are counted per destination: fr_dmx_bstats.hip's kernel over the partition
+// order, entered the same way.
 // The host inflates, normalises universal newlines (frender.py:776 reads in text mode), resolves
 // the rare codes outside the fast alphabet, raises the reference's errors, and gzips each
 // destination's bytes into its writer pair.
@@ -385,6 +388,9 @@ struct fr_dmx {
     DmxClassDest class_dest{};
     u64* rkey = nullptr;
     u64 rkey_cap = 0;
+    u8* rbin = nullptr;  // every R2 record's mismatch bin byte (fr_dmx_bstats_begin; else never allocated)
+    u64 rbin_cap = 0;
+    bool rbin_loaded = false;  // the R2 window at hand was classified with the bin bytes
     // per mate: data, record starts (+ sentinel), destinations (R2)
     u8* data[2] = {nullptr, nullptr};
     u64 cap[2] = {0, 0};
@@ -424,6 +430,10 @@ struct fr_dmx {
     // routed that no fr_dmx_cycles_window has added yet
     DmxCycles* cycles = nullptr;
     u64 cycles_ok = 0;
+    // the windows' index mismatch table (fr_dmx_bstats_begin; fr_dmx_bstats.hip), and the pairs the last fr_dmx_route
+    // routed that no fr_dmx_bstats_window has counted yet
+    DmxBstats* bstats = nullptr;
+    u64 bstats_ok = 0;
 };
 
 #define DK(x)                                                                  \
@@ -463,13 +473,14 @@ void fr_dmx_destroy(fr_dmx* d) {
     if (d->stream) (void)hipStreamSynchronize(d->stream);
     void* p[] = {d->tkeys, d->tvals, d->data[0], d->data[1], d->rs[0], d->rs[1], d->dest, d->out[0], d->out[1],
                  d->k_in, d->k_out, d->i_in, d->perm, d->first_pos, d->l1, d->l2, d->o1, d->o2, d->off1, d->off2,
-                 d->tmp, d->cnt, d->base, d->fe, d->row_dest, d->rkey};
+                 d->tmp, d->cnt, d->base, d->fe, d->row_dest, d->rkey, d->rbin};
     for (void* x : p)
         if (x) (void)hipFree(x);
     for (fr_defl* z : d->defl) fr_defl_destroy(z);
     dmx_tally_destroy(d->tally);
     dmx_stats_destroy(d->stats);
     dmx_cycles_destroy(d->cycles);
+    dmx_bstats_destroy(d->bstats);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
 }
@@ -542,7 +553,8 @@ int fr_dmx_set_sheet2(fr_dmx* d, fr_ctx* ctx, int num_subs1, int num_subs2, cons
 static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_records) {
     d->src[mate] = buf;
     d->len[mate] = len;
-    d->routed_ok = d->stats_ok = d->cycles_ok = 0;
+    d->routed_ok = d->stats_ok = d->cycles_ok = d->bstats_ok = 0;
+    if (mate == 1) d->rbin_loaded = false;
     const u32 ntiles = (u32)((len + DT - 1) / DT);
     DK(ensure(&d->cnt, d->c_cnt, (u64)ntiles + 1));
     DK(ensure(&d->base, d->c_base, (u64)ntiles + 1));
@@ -575,8 +587,10 @@ static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_re
         hipLaunchKernelGGL(dmx_index<true>, dim3(std::min<u32>(ntiles, 4096)), dim3(DWG), 0, d->stream, buf, len,
                            ntiles, d->base, d->rs[mate], d->dest, DmxTable{nullptr, nullptr, 0}, d->rkey);
         DK(hipGetLastError());
+        if (d->bstats) DK(ensure(&d->rbin, d->rbin_cap, nrec + 1));
         DK(launch_dmx_classify(d->rkey, d->dest, nrec, d->sheet, d->nsubs1, d->nsubs2, d->nbr, d->row_dest,
-                               d->class_dest, d->stream));
+                               d->class_dest, d->bstats ? d->rbin : nullptr, d->stream));
+        d->rbin_loaded = d->bstats != nullptr;
     } else if (ntiles) {
         DmxTable tab{d->tkeys, d->tvals, d->tmask};
         hipLaunchKernelGGL(dmx_index<false>, dim3(std::min<u32>(ntiles, 4096)), dim3(DWG), 0, d->stream, buf, len,
@@ -679,7 +693,7 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     if (P >= 0xFFFFFFFFull) return d->err = "too many records in one file pair", FR_ERR_CAPACITY;
     *first_error = -1;
     *error_val = 0;
-    d->routed_ok = d->stats_ok = d->cycles_ok = 0;
+    d->routed_ok = d->stats_ok = d->cycles_ok = d->bstats_ok = 0;
     for (int k = 0; k < n_dest; ++k) bytes_r1[k] = bytes_r2[k] = 0;
     d->out_len[0] = d->out_len[1] = 0;
     d->hoff[0].assign((size_t)std::max(n_dest, 0) + 1, 0);
@@ -760,6 +774,7 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     d->hoff[0] = h1;
     d->hoff[1] = h2;
     d->routed_ok = d->stats_ok = d->cycles_ok = P;
+    d->bstats_ok = d->rbin_loaded ? P : 0;
     return FR_OK;
 }
 
@@ -870,6 +885,54 @@ int fr_dmx_cycles_get(fr_dmx* d, int n_dest, int max_cycles, uint64_t* out) {
         return d->err = "fr_dmx_cycles_get: n_dest or max_cycles differs from fr_dmx_cycles_begin", FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     return dmx_cycles_get(d->cycles, out, d->err);
+}
+
+// ---- the windows' index mismatch table: mode and call order are checked here, the work is fr_dmx_bstats.hip's
+int fr_dmx_bstats_begin(fr_dmx* d, int n_dest) {
+    if (!d->key_mode) return d->err = "fr_dmx_bstats_begin: sheet mode only (fr_dmx_set_sheet)", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    d->bstats_ok = 0;
+    return dmx_bstats_begin(&d->bstats, d->device, d->stream, n_dest, d->err);
+}
+
+int fr_dmx_bstats_patch(fr_dmx* d, const uint64_t* recs, const uint8_t* bins, uint64_t n) {
+    if (!d->bstats || !d->rbin_loaded)
+        return d->err = "fr_dmx_bstats_patch: no R2 window loaded since fr_dmx_bstats_begin", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    for (u64 k = 0; k < n; ++k)
+        if (recs[k] >= d->nrec[1]) return d->err = "record index out of range", FR_ERR_INVALID;
+    if (n >= DMX_BATCH) {  // many records: the whole array there and back, two copies
+        std::vector<u8> all(d->nrec[1]);
+        DK(hipMemcpy(all.data(), d->rbin, all.size(), hipMemcpyDeviceToHost));
+        for (u64 k = 0; k < n; ++k) all[recs[k]] = bins[k];
+        DK(hipMemcpy(d->rbin, all.data(), all.size(), hipMemcpyHostToDevice));
+        return FR_OK;
+    }
+    for (u64 k = 0; k < n; ++k) DK(hipMemcpyAsync(d->rbin + recs[k], bins + k, 1, hipMemcpyHostToDevice, d->stream));
+    DK(hipStreamSynchronize(d->stream));
+    return FR_OK;
+}
+
+int fr_dmx_bstats_window(fr_dmx* d, uint64_t n_pairs) {
+    if (!d->bstats) return d->err = "fr_dmx_bstats_window: no fr_dmx_bstats_begin", FR_ERR_INVALID;
+    if (n_pairs != d->bstats_ok)
+        return d->err = "fr_dmx_bstats_window: n_pairs differs from the pairs the last fr_dmx_route routed (or they "
+                        "are counted already, or were classified before fr_dmx_bstats_begin)",
+               FR_ERR_INVALID;
+    if (d->hoff[0].size() > (size_t)dmx_bstats_n_dest(d->bstats) + 1)
+        return d->err = "fr_dmx_bstats_window: the last fr_dmx_route had more destinations than fr_dmx_bstats_begin",
+               FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    d->bstats_ok = 0;
+    return dmx_bstats_window(d->bstats, d->k_out, d->perm, d->rbin, n_pairs, d->err);
+}
+
+int fr_dmx_bstats_get(fr_dmx* d, int n_dest, uint64_t* out) {
+    if (!d->bstats) return d->err = "fr_dmx_bstats_get: no fr_dmx_bstats_begin", FR_ERR_INVALID;
+    if (n_dest != dmx_bstats_n_dest(d->bstats))
+        return d->err = "fr_dmx_bstats_get: n_dest differs from fr_dmx_bstats_begin", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    return dmx_bstats_get(d->bstats, out, d->err);
 }
 
 // the routed bytes of a mate through its fr_defl: gzip streams (crc32 set) or BGZF member runs

@@ -357,13 +357,17 @@ hipError_t launch_nbr_build(const SheetArgs& sh, const int32_t* canon, int nsubs
 // demux key mode (fr_demux.hip, fr_dmx_set_sheet): rec_dest[u] == DMX_PENDING marks a record whose fast key
 // dmx_index left in rec_key[u]; the launch replaces it with the record's destination: FR_DMX_NOPLUS /
 // FR_DMX_LEN1 / FR_DMX_LEN2 where classify_kernel reports error 3 / 1 / 2, row_dest[row] for a demuxable
-// code, class_dest[cls] otherwise.  Every other rec_dest entry is left as it is.
+// code, class_dest[cls] otherwise.  Every other rec_dest entry is left as it is.  rec_bin != nullptr
+// (fr_dmx_bstats_begin): every record's mismatch bin byte goes there too, bin1 * 5 + bin2 < DMX_BINS for a record
+// the launch classified and DMX_NO_BIN for every other one; nullptr: the kernel without that store.
 constexpr int32_t DMX_PENDING = INT32_MIN;
+constexpr int DMX_BINS = 25;      // (index-1 bin, index-2 bin): 0, 1, 2, 3 = three or more, 4 = none
+constexpr u8 DMX_NO_BIN = 255;    // a record without a bin byte (yet): the host's to patch, or an error
 struct DmxClassDest {
     int32_t v[4];        // by CLS_*
 };
 hipError_t launch_dmx_classify(const u64* rec_key, int32_t* rec_dest, u64 n, SheetArgs sh, int nsubs1, int nsubs2,
-                               const NbrMap& nm, const int32_t* row_dest, DmxClassDest cd, hipStream_t s);
+                               const NbrMap& nm, const int32_t* row_dest, DmxClassDest cd, u8* rec_bin, hipStream_t s);
 hipError_t launch_classify_cp(int n, const u32* q1, const int32_t* q1len, const u32* q2, const int32_t* q2len,
                               int stride, int S, const u32* s1, const int32_t* s1len, const u32* s2,
                               const int32_t* s2len, const u32* s2rc, const int32_t* name, int nsubs1, int nsubs2,
@@ -439,5 +443,16 @@ int dmx_cycles_max_cycles(const DmxCycles* t);
 int dmx_cycles_window(DmxCycles* t, const u8* out1, const u8* out2, const u64* o1, const u64* l1, const u64* o2,
                       const u64* l2, const u32* dest, u64 n, std::string& err);
 int dmx_cycles_get(DmxCycles* t, u64* out, std::string& err);
+
+// ---- the demux windows' index mismatch table (fr_dmx_bstats.hip; fr_demux.hip's fr_dmx_bstats_* entry points check
+// the mode and the call order and forward here).  acc[n_dest][5][5] u64 in HBM, owned by DmxBstats.  dest: the
+// sorted destination per partition position; perm: the pair index of every partition position; rec_bin: every R2
+// record's bin byte (launch_dmx_classify, fr_dmx_bstats_patch); n: the pairs routed.
+struct DmxBstats;
+int dmx_bstats_begin(DmxBstats** t, int device, hipStream_t stream, int n_dest, std::string& err);
+void dmx_bstats_destroy(DmxBstats* t);
+int dmx_bstats_n_dest(const DmxBstats* t);
+int dmx_bstats_window(DmxBstats* t, const u32* dest, const u32* perm, const u8* rec_bin, u64 n, std::string& err);
+int dmx_bstats_get(DmxBstats* t, u64* out, std::string& err);
 
 }  // namespace fr

@@ -17,6 +17,9 @@ bases >= Q30 and the quality sum -- over the routed records on the GPU (fr_dmx_s
 
 `--cycle-stats PATH` (both modes): the same pass counts, per output, mate and cycle (position in the read), the bases
 by value and the quality bytes, those >= Q30 and their sum (fr_dmx_cycles_*, CycleStats below).
+
+`--barcode-stats PATH` (-b): the same pass counts, per output, the pairs by mismatches in index 1 and in index 2 against
+their reference sheet row (fr_dmx_bstats_*, BarcodeStats below).
 """
 from __future__ import annotations
 
@@ -36,7 +39,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import (cycle_stats_path, demux_mode, get_indexes, gz_format, input_spec, limits_of, mismatch_limits,
+from .host import (barcode_stats_path, cycle_stats_path, demux_mode, get_indexes, gz_format, input_spec, limits_of, mismatch_limits,
                    num_subs_of, parse_files, report_args, single_index, stats_path)
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
@@ -423,6 +426,34 @@ def sheet_destinations(sheet_ids, route_of) -> tuple:
     return row_dest, class_dest
 
 
+BSTATS_BINS = ("0", "1", "2", "3+", "none")  # a mismatch bin's label; a bin byte is bin1 * 5 + bin2
+NO_BIN = 255  # the bin byte of a record without bins (a classification error: such a pair is never routed)
+
+
+def mismatch_bin(query, ref) -> int:
+    """Index of BSTATS_BINS: the positions at which query differs from the reference row's entry, case-folded (equal
+    lengths: the length check has passed), 3 for three or more; ref None: no reference row."""
+    if ref is None:
+        return 4
+    return min(sum(1 for a, b in zip(query.lower(), ref.lower()) if a != b), 3)
+
+
+def bin_byte(q1, q2, read_type: str, m1: int, m2: int, row: int, idx1, idx2, single: bool) -> int:
+    """A classified code's bin byte by `--barcode-stats`' definition.  The reference row of both indexes is the
+    assigned row of a demuxable code (not the first row idx1 matches: that row may be another sample's); of an
+    index hop or an ambiguous code the first row within the limit of index 1 (m1) and of index 2 (m2); an
+    undetermined code has none.  single: there is no index 2."""
+    if read_type == "undetermined":
+        r1 = r2 = -1
+    elif read_type == "demuxable":
+        r1 = r2 = row
+    else:
+        r1, r2 = m1, m2
+    b1 = mismatch_bin(q1, idx1[r1] if r1 >= 0 else None)
+    b2 = 4 if single else mismatch_bin(q2, idx2[r2] if r2 >= 0 else None)
+    return b1 * 5 + b2
+
+
 class SheetMode:
     """`demux -b SHEET -n N [--n1 A] [--n2 B]`: every pair's code is classified against the sample sheet as
     `scan` with the same limits classifies it (frender.py:214-291), per record on the GPU (fr_dmx_set_sheet /
@@ -438,6 +469,7 @@ class SheetMode:
         self.num_subs = num_subs_of(*(int(v) for v in limits_of(num_subs)))
         self.route_of = route_of
         self.memo = {}       # exotic code -> destination or FR_DMX_LEN1 / _LEN2 / _NOPLUS
+        self.bins = {}       # exotic code -> its bin byte (--barcode-stats), cached with the destination
         self.classified = 0  # exotic strings sent to the classifier (each distinct one once)
         self.ctx = None
         self.own_ctx = False
@@ -461,12 +493,13 @@ class SheetMode:
 
     def resolve(self, codes) -> list:
         """Destinations of exotic codes (scan.process's exotic branch: scan.split_exotic, classify_cp, the
-        same error rules)."""
+        same error rules).  Every code's bin byte is worked out from the same answer (bins_of)."""
         from .scan import split_exotic
         new = [c for c in dict.fromkeys(codes) if c not in self.memo]
         kept, q1, q2, bare = split_exotic(new, self.single)
         for k in bare:
             self.memo[new[k]] = _lib.FR_DMX_NOPLUS
+            self.bins[new[k]] = NO_BIN
         if kept:
             self.classified += len(kept)
             out = self.ctx.classify_cp(q1, q2, self.num_subs, False)
@@ -475,11 +508,18 @@ class SheetMode:
                 err = int(out["err"][k])
                 if err:
                     self.memo[c] = val_of.get(err, _lib.FR_DMX_NOPLUS)
+                    self.bins[c] = NO_BIN
                     continue
                 name = _lib.CLASS_NAMES[int(out["cls"][k])]
                 sid = self.ids[int(out["row"][k])] if name == "demuxable" else ""
                 self.memo[c] = self.route_of((name, sid))
+                self.bins[c] = bin_byte(q1[k], q2[k], name, int(out["m1"][k]), int(out["m2"][k]), int(out["row"][k]),
+                                        self.idx1, self.idx2, self.single)
         return [self.memo[c] for c in codes]
+
+    def bins_of(self, codes) -> list:
+        """The bin bytes of exotic codes resolve() has seen (fr_dmx_bstats_patch's bytes, beside its destinations)."""
+        return [self.bins[c] for c in codes]
 
     def error(self, code: str, val: int):
         """The exception scan raises for a code with classification error val (None: not such a value)."""
@@ -799,15 +839,86 @@ class CycleStats:
         self.write(self.path, names, self.sum_ranks([g.view(np.uint64).reshape(shape) for g in got]))
 
 
+BSTATS_HEADER = ["output", "idx1_mismatches", "idx2_mismatches", "reads", "pct_reads"]
+
+
+class BarcodeStats:
+    """`demux -b --barcode-stats PATH`: how well the barcodes matched.  The classifier leaves every record's bin byte
+    (bin_byte's definition; the host patches the records it resolved by string) and the GPU counts the routed pairs
+    of every window per destination and bin pair (Demux.bstats_*: fr_dmx_bstats.hip); this object turns the counts
+    into the CSV: per planned destination, in plan_destinations' order, one row per bin pair that any output has a
+    count in (the table is rectangular), index-1 bin first, bins in BSTATS_BINS' order."""
+
+    def __init__(self, path=None):
+        self.path = None if path is None else str(path)
+        self.n_dest = 0
+
+    def begin(self, dmx, n_dest: int):
+        self.n_dest = int(n_dest)
+        dmx.bstats_begin(self.n_dest)
+
+    def patch(self, dmx, ex, bins):
+        """The records the host resolved (beside Demux.patch): their bin bytes."""
+        dmx.bstats_patch(ex, np.array(bins, dtype=np.uint8))
+
+    def window(self, dmx, n_pairs: int):
+        """The window's first n_pairs records are routed: count them."""
+        dmx.bstats_window(n_pairs)
+
+    def local(self, dmx) -> np.ndarray:
+        """This process's counts once its last pair is done: uint64 [n_dest, 5, 5]."""
+        return dmx.bstats_get(self.n_dest)
+
+    @staticmethod
+    def sum_ranks(arrays) -> np.ndarray:
+        """The counts of several ranks as one: [n_dest, 5, 5]."""
+        return np.sum([np.asarray(a, dtype=np.uint64) for a in arrays], axis=0, dtype=np.uint64)
+
+    @staticmethod
+    def rows(names, array) -> list:
+        """The CSV's rows without the header; array [len(names), 5, 5].  pct_reads: of the output's own reads, empty
+        for an output without any."""
+        a = np.asarray(array)
+        nb = len(BSTATS_BINS)
+        assert a.shape == (len(names), nb, nb), "barcode stats: the array is not [destinations, 5, 5]"
+        used = [(i, j) for i in range(nb) for j in range(nb) if a[:, i, j].any()]
+        out = []
+        for k, name in enumerate(names):
+            total = sum(int(a[k, i, j]) for i, j in used)
+            for i, j in used:
+                reads = int(a[k, i, j])
+                out.append([name, BSTATS_BINS[i], BSTATS_BINS[j], reads, f"{100 * reads / total:.2f}" if total else ""])
+        return out
+
+    def write(self, path, names, array):
+        with open(path, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(BSTATS_HEADER)
+            w.writerows(self.rows(names, array))
+
+    def write_ranks(self, group, wire, array, names):
+        """`--gpus N`, no rank failed: every rank's counts go to rank 0, which adds them and writes the file."""
+        import torch
+
+        from .dist import gather_rows
+        nb = len(BSTATS_BINS)
+        got = gather_rows(group, wire, torch.from_numpy(np.ascontiguousarray(array).view(np.int64).reshape(-1, nb * nb)))
+        if group.get_rank() != 0:
+            return
+        shape = (len(names), nb, nb)
+        self.write(self.path, names, self.sum_ranks([g.view(np.uint64).reshape(shape) for g in got]))
+
+
 def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of, writers, window, sheet=None,
-                hit=None, report=None, stats=None, cycles=None):
+                hit=None, report=None, stats=None, cycles=None, bstats=None):
     """One R1/R2 pair in record-aligned windows: the GPU indexes both windows, the complete
     record pairs are routed, and the bytes after the last routed record carry into the next
     window.  Pairing stops when either mate runs out of records (zip, frender.py:777).  The mates
     inflate on the native pool gz (files i1, i2).  sheet (SheetMode): `demux -b`, no results; hit: a set
     that collects the destinations pairs were routed to; report (Report, after its begin_pair): `--report`, every
     routed window is counted; stats (Stats, after its begin): `--stats`, every routed window is summed; cycles
-    (CycleStats, after its begin): `--cycle-stats`, every routed window is counted per cycle."""
+    (CycleStats, after its begin): `--cycle-stats`, every routed window is counted per cycle; bstats (BarcodeStats,
+    after its begin, with sheet): `--barcode-stats`, every routed window is counted per mismatch bin pair."""
     streams =[text_chunks(read1_file, gz, i1), text_chunks(read2_file, gz, i2)]
     bufs = [[], []]  # each mate's window as a list of decoded blocks (never joined on the host)
     eof = [False, False]
@@ -845,6 +956,8 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 dest = sheet.resolve(codes) if sheet is not None else \
                     [route_of(results[c]) if c in results else _lib.FR_DMX_MISSING for c in codes]
                 dmx.patch(ex, np.array(dest, dtype=np.int32))
+                if bstats is not None:  # the same records' bin bytes, from the same answers
+                    bstats.patch(dmx, ex, sheet.bins_of(codes))
             first, val, b1, b2 = dmx.route(len(writers), n_pairs)
             t3 = clock()
             if first >= 0:
@@ -862,6 +975,8 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 stats.window(dmx, n_pairs)
             if cycles is not None:  # the same, per cycle
                 cycles.window(dmx, n_pairs)
+            if bstats is not None:  # the routed records' bin bytes, in partition order
+                bstats.window(dmx, n_pairs)
             if hit is not None:
                 hit.update(np.nonzero(b1 + b2)[0].tolist())
             # each mate's bytes for the files and their per-destination sizes, as the writers' family makes them
@@ -971,6 +1086,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     report_path, prefix = report_args(args)
     stats_file = stats_path(args)
     cycles_file = cycle_stats_path(args)
+    bstats_file = barcode_stats_path(args)
     fmt = gz_format(args)
     single = single_index(args)
     num_subs = num_subs_of(*mismatch_limits(args)) if mode == "b" else None  # --n2 with --single-index: refused here
@@ -1012,6 +1128,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     report = Report(report_path, prefix) if report_path is not None else None  # --report (with -b: report_args)
     stats = Stats(stats_file) if stats_file is not None else None  # --stats
     cycles = CycleStats(cycles_file) if cycles_file is not None else None  # --cycle-stats
+    bstats = BarcodeStats(bstats_file) if bstats_file is not None else None  # --barcode-stats (with -b)
 
     table = None
     if mode == "r":
@@ -1024,7 +1141,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     window = int(getattr(args, "window", None) or (512 << 20))  # decoded bytes per mate per GPU pass
     if group is not None:
         return _demux_ranks(group, args, pairs, results, route_of, table, writers, window, level, infix, kind, sheet,
-                            lazy, t_start, report, stats, cycles)
+                            lazy, t_start, report, stats, cycles, bstats)
     paths = [str(f) for pr in pairs for f in pr]
     try:
         with _session(t_start, paths, kind, len(writers), _device_index(None), sheet, table, dev, ctx,
@@ -1035,12 +1152,14 @@ def frender_demux(args, dev=None, ctx=None) -> None:
                 stats.begin(dmx, len(names))
             if cycles is not None:
                 cycles.begin(dmx, len(names))
+            if bstats is not None:
+                bstats.begin(dmx, len(names))
             for k, (read1_file, read2_file) in enumerate(pairs):
                 print(f"Demultiplexing {read1_file.name}...")
                 if report is not None:
                     report.begin_pair(dmx, k)
                 _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers,
-                            window, sheet, hit, report, stats, cycles)
+                            window, sheet, hit, report, stats, cycles, bstats)
             if sheet is not None and samples and not (hit & lazy):
                 print(NO_SAMPLES_WARNING)  # known only now: no pair was demuxable
             if report is not None:  # every pair is routed: the table is complete
@@ -1051,6 +1170,9 @@ def frender_demux(args, dev=None, ctx=None) -> None:
             if cycles is not None:
                 print(f"Writing demux cycle statistics to {cycles.path}")
                 cycles.write(cycles.path, names, cycles.local(dmx))
+            if bstats is not None:
+                print(f"Writing demux barcode statistics to {bstats.path}")
+                bstats.write(bstats.path, names, bstats.local(dmx))
     finally:
         STAGE_TIMES["total"] = time.perf_counter() - t_start
         if getattr(args, "stage_times", False):
@@ -1107,7 +1229,7 @@ def _mkdir_everywhere(group, path):
 
 
 def _demux_ranks(group, args, pairs, results, route_of, table, names, window, level, infix, kind, sheet, lazy,
-                 t_start, report=None, stats=None, cycles=None):
+                 t_start, report=None, stats=None, cycles=None, bstats=None):
     import shutil
 
     from .dist import PeerFailed, reduce_min
@@ -1118,6 +1240,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
     tally = None  # --report: this rank's table, once its last pair is done
     sums = None  # --stats: this rank's sums, once its last pair is done
     counts = None  # --cycle-stats: this rank's counts, once its last pair is done
+    bcounts = None  # --barcode-stats: this rank's counts, once its last pair is done
     try:
         # the session opens inside the try: a rank whose pool or device fails still joins the collectives below
         # (-b: this rank's own sheet context: classification is stateless, nothing is exchanged)
@@ -1129,6 +1252,8 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                 stats.begin(dmx, len(names))
             if cycles is not None:
                 cycles.begin(dmx, len(names))
+            if bstats is not None:
+                bstats.begin(dmx, len(names))
             for j, k in enumerate(mine):
                 d = os.path.join(parts, str(k))
                 os.makedirs(d, exist_ok=True)
@@ -1138,7 +1263,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                     if report is not None:
                         report.begin_pair(dmx, k)  # the global pair index: the ordinals are the one-process run's
                     _demux_pair(dmx, pool, gz, 2 * j, 2 * j + 1, pairs[k][0], pairs[k][1], results, route_of, writers,
-                                window, sheet, hit, report, stats, cycles)
+                                window, sheet, hit, report, stats, cycles, bstats)
                 except (Exception, SystemExit) as e:  # re-raised below if it is the first in pair order
                     failed, exc = k, e
                 finally:
@@ -1151,6 +1276,8 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                 sums = stats.local(dmx)
             if cycles is not None and exc is None:
                 counts = cycles.local(dmx)
+            if bstats is not None and exc is None:
+                bcounts = bstats.local(dmx)
     except (Exception, SystemExit) as e:  # before any pair (the device, the table): this rank's first pair
         if exc is None:
             failed, exc = (mine[0] if mine else len(pairs)), e
@@ -1198,3 +1325,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
         if rank == 0:
             print(f"Writing demux cycle statistics to {cycles.path}")
         cycles.write_ranks(group, _wire(group), counts, names)
+    if bstats is not None:  # after --cycle-stats' line
+        if rank == 0:
+            print(f"Writing demux barcode statistics to {bstats.path}")
+        bstats.write_ranks(group, _wire(group), bcounts, names)

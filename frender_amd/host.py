@@ -230,6 +230,26 @@ def cycle_stats_path(args):
     return path
 
 
+def barcode_stats_path(args):
+    """--barcode-stats PATH of a demux's arguments, or None (a namespace without the field has no index mismatch
+    table).  It goes with -b only (table mode classifies nothing, and the results file already holds idx1 and
+    matched_idx1 per code), and cannot be the file of --report, --stats or --cycle-stats.  Called with
+    cycle_stats_path, before anything is opened or created."""
+    path = getattr(args, "barcode_stats", None)
+    if path is None:
+        return None
+    if getattr(args, "b", None) is None:
+        raise SystemExit("demux --barcode-stats: belongs to -b (with -r nothing is classified here: the result file "
+                         "holds idx1 and matched_idx1 per code)")
+    here = os.path.abspath(os.fspath(path))
+    for flag, other in (("--report", getattr(args, "report", None)), ("--stats", getattr(args, "stats", None)),
+                        ("--cycle-stats", getattr(args, "cycle_stats", None))):
+        if other is not None and os.path.abspath(os.fspath(other)) == here:
+            raise SystemExit(f"demux --barcode-stats: the index mismatch table and {flag} cannot be written to the "
+                             "same file")
+    return path
+
+
 def gz_format(args) -> str:
     """--gz-format of a demux's arguments (a namespace without it means gzip), checked against --gz-writer:
     only the GPU writer makes BGZF.  Called before anything is opened or created."""

@@ -503,6 +503,31 @@ int fr_dmx_cycles_window(fr_dmx* d, uint64_t n_pairs);
  * q30_bases, quality_raw_sum}; n_dest and max_cycles as begun.  Synchronises. */
 int fr_dmx_cycles_get(fr_dmx* d, int n_dest, int max_cycles, uint64_t* out);
 
+/* ---- the demux windows' index mismatch table (`demux -b --barcode-stats`; fr_dmx_bstats.hip): how well the routed
+ * pairs' barcodes matched, per destination.  Sheet mode only.  Every R2 record gets one bin byte, bin1 * 5 + bin2:
+ * bin k is the number of positions at which the read's index k differs from its reference row's (0, 1, 2, 3 = three
+ * or more), or 4 = none.  The reference row of both indexes is the assigned row of a demuxable code; of a hop or an
+ * ambiguous code it is the first row within the limit of index 1 and the first within the limit of index 2; an
+ * undetermined code has none, and a single-index sheet has no index 2.  The classifier sets the byte of every record
+ * it classifies, 255 for every other one (exotic, no '+', length errors); the host sets the bytes of the records it
+ * resolves.  Every call below returns FR_ERR_INVALID, with the counts untouched, when the order described is not
+ * kept. */
+/* Start (or clear) the table of a demux in sheet mode (FR_ERR_INVALID in table mode): n_dest destinations, all
+ * counts zero.  Off, nothing allocated and the classifier as it was, until this call; from here on every
+ * fr_dmx_load* of mate 1 also leaves the records' bin bytes. */
+int fr_dmx_bstats_begin(fr_dmx* d, int n_dest);
+/* Set the bin bytes of the given R2 records of the window at hand (the host's resolution of exotic codes, beside
+ * fr_dmx_patch).  FR_ERR_INVALID for a record out of range, or with no window loaded since fr_dmx_bstats_begin. */
+int fr_dmx_bstats_patch(fr_dmx* d, const uint64_t* recs, const uint8_t* bins, uint64_t n);
+/* Count the n_pairs record pairs the last fr_dmx_route routed (it found no negative destination; n_pairs must be
+ * its count; a window is counted once; its R2 records were loaded after fr_dmx_bstats_begin; that route's n_dest is
+ * at most the begun one).  A bin byte above 24 is not counted.  Independent of the other *_window calls.  Queues on
+ * the context's stream and makes no synchronisation of its own. */
+int fr_dmx_bstats_window(fr_dmx* d, uint64_t n_pairs);
+/* out[n_dest][5][5]: per destination, index-1 bin and index-2 bin the pairs counted; n_dest as begun.
+ * Synchronises. */
+int fr_dmx_bstats_get(fr_dmx* d, int n_dest, uint64_t* out);
+
 /* ---- GPU deflate over any byte ranges (fr_deflate.hip; fr_dmx_deflate runs it on the routed bytes).
  * Stream s is bytes [offsets[s], offsets[s + 1]) of the device buffer dev_data (4-byte aligned, 16
  * readable bytes past offsets[n_streams]); every stream becomes one raw deflate stream, no larger than
