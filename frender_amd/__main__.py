@@ -103,6 +103,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "mismatches in index 1 and in index 2 (0, 1, 2, 3+ or none) against the sheet row the read was "
                         "assigned to (demuxable) or the first row each index matches (index hop, ambiguous); counted "
                         "on the GPU in the same pass")
+    d.add_argument("--validate", action="store_true",
+                   help="check every record pair on the GPU before it is routed, in the same pass, and end with an "
+                        "error that names the first bad pair: a record of fewer than four lines, a header line "
+                        "without '@', a third line without '+', a quality line whose length differs from its "
+                        "sequence's, mates whose read names or barcodes differ, or one mate with records left after "
+                        "the other's last (-r and -b)")
     d.add_argument("--strict-header", action="store_true",
                    help="reject a results file in scan's own column order, as frender.py does (default: accept it)")
     d.add_argument("--gz-level", type=int, default=None,

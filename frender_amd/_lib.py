@@ -181,6 +181,10 @@ _SIGS = {
     "fr_dmx_bstats_patch": (C.c_int, [P, P, P, C.c_uint64]),
     "fr_dmx_bstats_window": (C.c_int, [P, C.c_uint64]),
     "fr_dmx_bstats_get": (C.c_int, [P, C.c_int, P]),
+    "fr_dmx_validate_begin": (C.c_int, [P]),
+    "fr_dmx_validate_window": (C.c_int, [P, C.c_uint64]),
+    "fr_dmx_validate_result": (C.c_int, [P, P, P]),
+    "fr_dmx_validate_end": (C.c_int, [P]),
     "fr_defl_create": (P, [C.c_int]),
     "fr_defl_destroy": (None, [P]),
     "fr_defl_last_error": (C.c_char_p, [P]),
@@ -288,6 +292,9 @@ def pack_lower(s: str) -> int:
 FR_INDEX_DUAL, FR_INDEX_SINGLE = 0, 1  # fr_set_index_mode
 FR_DMX_MISSING, FR_DMX_BADTYPE, FR_DMX_EXOTIC = -1, -2, -3
 FR_DMX_LEN1, FR_DMX_LEN2, FR_DMX_NOPLUS = -4, -5, -6  # sheet mode: scan's error 1, 2, 3 for the code
+# fr_dmx_validate_result's kinds: 1-4 of R1's record, + FR_DMX_V_R2 of R2's, then the pair's
+FR_DMX_V_TRUNCATED, FR_DMX_V_HEADER, FR_DMX_V_SEPARATOR, FR_DMX_V_LENGTH, FR_DMX_V_R2 = 1, 2, 3, 4, 4
+FR_DMX_V_NAME, FR_DMX_V_CODE = 9, 10
 
 
 _PACK_LUT = np.zeros(128, dtype=np.uint8)
@@ -676,6 +683,23 @@ class Demux:
         out = np.zeros((max(int(n_dest), 0), 5, 5), np.uint64)
         self._ck(lib.fr_dmx_bstats_get(self.h, int(n_dest), _ptr(out)), "fr_dmx_bstats_get")
         return out
+
+    # ---- the windows' validation (demux --validate; fr_dmx_validate_*) ---------------------
+    def validate_begin(self):
+        self._ck(lib.fr_dmx_validate_begin(self.h), "fr_dmx_validate_begin")
+
+    def validate_window(self, n_pairs: int):
+        """Check the first n_pairs record pairs of the window both load*() calls left (queued, no wait)."""
+        self._ck(lib.fr_dmx_validate_window(self.h, int(n_pairs)), "fr_dmx_validate_window")
+
+    def validate_result(self) -> tuple:
+        """(first violating pair of the last queued window, its kind: FR_DMX_V_*), or (-1, 0)."""
+        fp, kind = C.c_int64(), C.c_int32()
+        self._ck(lib.fr_dmx_validate_result(self.h, C.byref(fp), C.byref(kind)), "fr_dmx_validate_result")
+        return fp.value, kind.value
+
+    def validate_end(self):
+        self._ck(lib.fr_dmx_validate_end(self.h), "fr_dmx_validate_end")
 
 
 class Deflater:

@@ -434,6 +434,11 @@ struct fr_dmx {
     // routed that no fr_dmx_bstats_window has counted yet
     DmxBstats* bstats = nullptr;
     u64 bstats_ok = 0;
+    // the windows' validation (fr_dmx_validate_begin; fr_dmx_validate.hip): the mates loaded since the last
+    // fr_dmx_validate_window, and whether a window is queued whose result can be read
+    DmxValidate* validate = nullptr;
+    bool vloaded[2] = {false, false};
+    bool vqueued = false;
 };
 
 #define DK(x)                                                                  \
@@ -481,6 +486,7 @@ void fr_dmx_destroy(fr_dmx* d) {
     dmx_stats_destroy(d->stats);
     dmx_cycles_destroy(d->cycles);
     dmx_bstats_destroy(d->bstats);
+    dmx_validate_destroy(d->validate);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
 }
@@ -554,6 +560,7 @@ static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_re
     d->src[mate] = buf;
     d->len[mate] = len;
     d->routed_ok = d->stats_ok = d->cycles_ok = d->bstats_ok = 0;
+    d->vloaded[mate] = false;
     if (mate == 1) d->rbin_loaded = false;
     const u32 ntiles = (u32)((len + DT - 1) / DT);
     DK(ensure(&d->cnt, d->c_cnt, (u64)ntiles + 1));
@@ -598,6 +605,7 @@ static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_re
         DK(hipGetLastError());
     }
     DK(hipStreamSynchronize(d->stream));
+    d->vloaded[mate] = true;
     return FR_OK;
 }
 
@@ -933,6 +941,44 @@ int fr_dmx_bstats_get(fr_dmx* d, int n_dest, uint64_t* out) {
         return d->err = "fr_dmx_bstats_get: n_dest differs from fr_dmx_bstats_begin", FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     return dmx_bstats_get(d->bstats, out, d->err);
+}
+
+// ---- the windows' validation: the call order is checked here, the work is fr_dmx_validate.hip's
+int fr_dmx_validate_begin(fr_dmx* d) {
+    DK(hipSetDevice(d->device));
+    d->vqueued = false;
+    return dmx_validate_begin(&d->validate, d->device, d->stream, d->err);
+}
+
+int fr_dmx_validate_window(fr_dmx* d, uint64_t n_pairs) {
+    if (!d->validate) return d->err = "fr_dmx_validate_window: no fr_dmx_validate_begin", FR_ERR_INVALID;
+    if (!d->vloaded[0] || !d->vloaded[1])
+        return d->err = "fr_dmx_validate_window: not both mates are loaded since the last fr_dmx_validate_window",
+               FR_ERR_INVALID;
+    if (n_pairs > std::min(d->nrec[0], d->nrec[1]))
+        return d->err = "fr_dmx_validate_window: n_pairs is beyond a mate's records", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    const int rc = dmx_validate_window(d->validate, d->src[0], d->src[1], d->rs[0], d->rs[1], n_pairs, d->err);
+    if (rc == FR_OK) {
+        d->vloaded[0] = d->vloaded[1] = false;
+        d->vqueued = true;
+    }
+    return rc;
+}
+
+int fr_dmx_validate_result(fr_dmx* d, int64_t* first_pair, int32_t* kind) {
+    if (!d->validate || !d->vqueued)
+        return d->err = "fr_dmx_validate_result: no fr_dmx_validate_window is queued", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    return dmx_validate_result(d->validate, first_pair, kind, d->err);
+}
+
+int fr_dmx_validate_end(fr_dmx* d) {
+    DK(hipSetDevice(d->device));
+    dmx_validate_destroy(d->validate);  // (waits for the stream: a queued window still writes the word)
+    d->validate = nullptr;
+    d->vqueued = false;
+    return FR_OK;
 }
 
 // the routed bytes of a mate through its fr_defl: gzip streams (crc32 set) or BGZF member runs

@@ -27,6 +27,14 @@ __device__ __forceinline__ u32 nl_mask16(const uint4& v) {  // '\n' bytes of 16 
            (eq4(v.w, 0x0A0A0A0Au) << 12);
 }
 
+__device__ __forceinline__ u32 eq_mask16(const uint4& v, u32 rep) {  // bytes of 16 equal to rep's byte -> bits 0..15
+    return eq4(v.x, rep) | (eq4(v.y, rep) << 4) | (eq4(v.z, rep) << 8) | (eq4(v.w, rep) << 12);
+}
+
+__device__ __forceinline__ u32 either_mask16(const uint4& v, u32 rep_a, u32 rep_b) {  // equal to either of two bytes
+    return eq_mask16(v, rep_a) | eq_mask16(v, rep_b);
+}
+
 // bits i of 0..15 with lo <= p + i < hi
 __device__ __forceinline__ u32 span_mask(u64 p, u64 lo, u64 hi) {
     const u32 s = lo > p ? (u32)min(lo - p, (u64)16) : 0u;

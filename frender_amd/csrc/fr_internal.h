@@ -455,4 +455,14 @@ int dmx_bstats_n_dest(const DmxBstats* t);
 int dmx_bstats_window(DmxBstats* t, const u32* dest, const u32* perm, const u8* rec_bin, u64 n, std::string& err);
 int dmx_bstats_get(DmxBstats* t, u64* out, std::string& err);
 
+// ---- the demux windows' validation (fr_dmx_validate.hip; fr_demux.hip's fr_dmx_validate_* entry points check the
+// call order and forward here).  One u64 result word in HBM, owned by DmxValidate.  b1/b2: the unrouted bytes of
+// the mates (16 bytes of slack past the last record); rs1/rs2: their record starts and the sentinel; n: the pairs.
+struct DmxValidate;
+int dmx_validate_begin(DmxValidate** t, int device, hipStream_t stream, std::string& err);
+void dmx_validate_destroy(DmxValidate* t);
+int dmx_validate_window(DmxValidate* t, const u8* b1, const u8* b2, const u64* rs1, const u64* rs2, u64 n,
+                        std::string& err);
+int dmx_validate_result(DmxValidate* t, int64_t* first_pair, int32_t* kind, std::string& err);
+
 }  // namespace fr

@@ -20,6 +20,10 @@ by value and the quality bytes, those >= Q30 and their sum (fr_dmx_cycles_*, Cyc
 
 `--barcode-stats PATH` (-b): the same pass counts, per output, the pairs by mismatches in index 1 and in index 2 against
 their reference sheet row (fr_dmx_bstats_*, BarcodeStats below).
+
+`--validate` (both modes): the same pass checks every record pair before it is routed -- four lines, '@', '+', equal
+sequence and quality lengths, equal read names and barcodes in both mates -- on the GPU (fr_dmx_validate_*, Validate
+below), and the host checks that neither mate has records left after the other's last; the first bad pair ends the run.
 """
 from __future__ import annotations
 
@@ -40,7 +44,7 @@ import numpy as np
 
 from . import _lib
 from .host import (barcode_stats_path, cycle_stats_path, demux_mode, get_indexes, gz_format, input_spec, limits_of, mismatch_limits,
-                   num_subs_of, parse_files, report_args, single_index, stats_path)
+                   num_subs_of, parse_files, report_args, single_index, stats_path, validate_flag)
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
 # the column order `scan` itself writes (frender.py:482-501, report_analysis)
@@ -374,6 +378,19 @@ def _tail(parts, start: int) -> list:
             return ([p[start:]] if start else [p]) + parts[k + 1:]
         start -= len(p)
     return []
+
+
+def _span(parts, start: int, end: int) -> bytes:
+    """Bytes [start, end) of the concatenation of `parts`."""
+    out = []
+    for p in parts:
+        if end <= 0:
+            break
+        if start < len(p):
+            out.append(p[max(start, 0):end])
+        start -= len(p)
+        end -= len(p)
+    return b"".join(out)
 
 
 def _code_at(bufs, start: int) -> str:
@@ -909,8 +926,65 @@ class BarcodeStats:
         self.write(self.path, names, self.sum_ranks([g.view(np.uint64).reshape(shape) for g in got]))
 
 
+V_KINDS = ("truncated", "header", "separator", "length")  # kinds 1-4 of R1's record, 5-8 of R2's (_lib.FR_DMX_V_*)
+V_NAME, V_CODE, V_COUNT = 9, 10, 11  # the pair's kinds, and the file pair's (the host's own)
+
+
+def name_token(header: bytes) -> bytes:
+    """`--validate`'s name of a header line: after the '@' up to the first space or tab, without a last /1 or /2."""
+    t = re.split(rb"[ \t]", header[1:], maxsplit=1)[0]
+    return t[:-2] if t[-2:] in (b"/1", b"/2") else t
+
+
+class Validate:
+    """`demux --validate`: every pair that would be routed is checked first.  The GPU checks the pairs of every window
+    over the unrouted bytes (Demux.validate_*: fr_dmx_validate.hip) and reports the first bad pair and its kind; this
+    object words the error from the window's host bytes.  Kind 11 (a mate with records left after the other's last) is
+    _demux_pair's to find, where its loop ends."""
+
+    def begin(self, dmx):
+        dmx.validate_begin()
+
+    def window(self, dmx, n_pairs: int):
+        """Both mates' windows are loaded: queue the check of their first n_pairs pairs, ahead of the route."""
+        dmx.validate_window(n_pairs)
+
+    def result(self, dmx) -> tuple:
+        """(first bad pair of the queued window, its kind) or (-1, 0); after the route, which has waited already."""
+        return dmx.validate_result()
+
+    def end(self, dmx):
+        dmx.validate_end()
+
+    @staticmethod
+    def message(r1: str, r2: str, k: int, kind: int, rec1: bytes = b"", rec2: bytes = b"", left: int = 0) -> str:
+        """The error of pair k (1-based in the file pair r1 / r2) with violation `kind`; rec1, rec2: the mates' records
+        (kinds 1-10); left: the read (1 or 2) that has records left (kind 11)."""
+        def text(b):
+            return b.decode("utf-8", "replace")
+
+        head = f"demux --validate: {r1} / {r2}, record {k}: "
+        if kind == V_COUNT:
+            return head + f"read {left} has records left after read {3 - left}'s last"
+        h1, h2 = rec1.split(b"\n")[0], rec2.split(b"\n")[0]
+        if kind == V_NAME:
+            return head + f"read names differ: {text(name_token(h1))!r} and {text(name_token(h2))!r}"
+        if kind == V_CODE:
+            return head + f"barcodes differ: {text(h1.split(b':')[-1])!r} in read 1, {text(h2.split(b':')[-1])!r} in read 2"
+        m, rec = (1, rec1) if kind <= 4 else (2, rec2)
+        what = V_KINDS[(kind - 1) % 4]
+        if what == "truncated":
+            return head + f"read {m} record has fewer than four lines"
+        if what == "header":
+            return head + f"read {m} header line does not start with '@'"
+        if what == "separator":
+            return head + f"read {m} third line does not start with '+'"
+        pieces = rec.split(b"\n")
+        return head + f"read {m} sequence has {len(pieces[1])} bases, its quality line {len(pieces[3])} bytes"
+
+
 def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of, writers, window, sheet=None,
-                hit=None, report=None, stats=None, cycles=None, bstats=None):
+                hit=None, report=None, stats=None, cycles=None, bstats=None, validate=None):
     """One R1/R2 pair in record-aligned windows: the GPU indexes both windows, the complete
     record pairs are routed, and the bytes after the last routed record carry into the next
     window.  Pairing stops when either mate runs out of records (zip, frender.py:777).  The mates
@@ -918,7 +992,12 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
     that collects the destinations pairs were routed to; report (Report, after its begin_pair): `--report`, every
     routed window is counted; stats (Stats, after its begin): `--stats`, every routed window is summed; cycles
     (CycleStats, after its begin): `--cycle-stats`, every routed window is counted per cycle; bstats (BarcodeStats,
-    after its begin, with sheet): `--barcode-stats`, every routed window is counted per mismatch bin pair."""
+    after its begin, with sheet): `--barcode-stats`, every routed window is counted per mismatch bin pair; validate
+    (Validate, after its begin): `--validate`, every window's pairs are checked before they are routed, the earlier of
+    the first bad pair and the route's first error is raised (the bad pair at a tie: a malformed record's code means
+    nothing), and at the end neither mate may have a record left."""
+    mates = [os.path.basename(str(read1_file)), os.path.basename(str(read2_file))]
+    n_routed = 0  # pairs routed so far: --validate's record numbers count from the file pair's first
     streams =[text_chunks(read1_file, gz, i1), text_chunks(read2_file, gz, i2)]
     bufs = [[], []]  # each mate's window as a list of decoded blocks (never joined on the host)
     eof = [False, False]
@@ -944,10 +1023,12 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
             done = [n[m] if eof[m] else max(n[m] - 1, 0) for m in (0, 1)]
             n_pairs = min(done)
             if n_pairs == 0:
-                if eof[0] or eof[1] or (not n[0] and not n[1]):
+                if (eof[0] and not n[0]) or (eof[1] and not n[1]):  # a mate is out of records
                     break
                 window *= 2  # a record longer than the window: widen it
                 continue
+            if validate is not None:  # queued behind the loads, ahead of the route: nothing waits for it here
+                validate.window(dmx, n_pairs)
             ex = dmx.exotic(n_pairs)
             codes = []
             if ex.size:  # codes outside the fast alphabet: resolve by string
@@ -960,6 +1041,11 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                     bstats.patch(dmx, ex, sheet.bins_of(codes))
             first, val, b1, b2 = dmx.route(len(writers), n_pairs)
             t3 = clock()
+            if validate is not None:
+                bad, kind = validate.result(dmx)
+                if bad >= 0 and (first < 0 or bad <= first):  # the earlier pair; at the same pair the validation
+                    recs = [_span(bufs[m], *(int(v[0]) for v in dmx.records(m, [bad]))) for m in (0, 1)]
+                    raise SystemExit(Validate.message(*mates, n_routed + bad + 1, kind, *recs))
             if first >= 0:
                 s, _ = dmx.records(1, [first])
                 code = _code_at(bufs, int(s[0]))
@@ -979,6 +1065,7 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 bstats.window(dmx, n_pairs)
             if hit is not None:
                 hit.update(np.nonzero(b1 + b2)[0].tolist())
+            n_routed += n_pairs
             # each mate's bytes for the files and their per-destination sizes, as the writers' family makes them
             wins = [type(writers[0]["R1"]).window(dmx, m, len(writers), b) for m, b in ((0, b1), (1, b2))]
             t4 = clock()
@@ -1005,6 +1092,11 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                     bufs[m] = []
             if (eof[0] and n_pairs == n[0]) or (eof[1] and n_pairs == n[1]):
                 break
+        if validate is not None:
+            # a mate has a record left if it holds a byte past the routed records, or its stream yields one more
+            more = [any(len(p) for p in bufs[m]) or (not eof[m] and next(streams[m], None) is not None) for m in (0, 1)]
+            if more[0] != more[1]:
+                raise SystemExit(Validate.message(*mates, n_routed + 1, V_COUNT, left=1 if more[0] else 2))
     finally:
         for j in pending:
             j.result()
@@ -1129,6 +1221,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     stats = Stats(stats_file) if stats_file is not None else None  # --stats
     cycles = CycleStats(cycles_file) if cycles_file is not None else None  # --cycle-stats
     bstats = BarcodeStats(bstats_file) if bstats_file is not None else None  # --barcode-stats (with -b)
+    validate = Validate() if validate_flag(args) else None  # --validate
 
     table = None
     if mode == "r":
@@ -1141,7 +1234,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     window = int(getattr(args, "window", None) or (512 << 20))  # decoded bytes per mate per GPU pass
     if group is not None:
         return _demux_ranks(group, args, pairs, results, route_of, table, writers, window, level, infix, kind, sheet,
-                            lazy, t_start, report, stats, cycles, bstats)
+                            lazy, t_start, report, stats, cycles, bstats, validate)
     paths = [str(f) for pr in pairs for f in pr]
     try:
         with _session(t_start, paths, kind, len(writers), _device_index(None), sheet, table, dev, ctx,
@@ -1154,12 +1247,18 @@ def frender_demux(args, dev=None, ctx=None) -> None:
                 cycles.begin(dmx, len(names))
             if bstats is not None:
                 bstats.begin(dmx, len(names))
-            for k, (read1_file, read2_file) in enumerate(pairs):
-                print(f"Demultiplexing {read1_file.name}...")
-                if report is not None:
-                    report.begin_pair(dmx, k)
-                _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers,
-                            window, sheet, hit, report, stats, cycles, bstats)
+            if validate is not None:
+                validate.begin(dmx)
+            try:
+                for k, (read1_file, read2_file) in enumerate(pairs):
+                    print(f"Demultiplexing {read1_file.name}...")
+                    if report is not None:
+                        report.begin_pair(dmx, k)
+                    _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers,
+                                window, sheet, hit, report, stats, cycles, bstats, validate)
+            finally:
+                if validate is not None:  # a caller's dev goes back as it came: the validation off
+                    validate.end(dmx)
             if sheet is not None and samples and not (hit & lazy):
                 print(NO_SAMPLES_WARNING)  # known only now: no pair was demuxable
             if report is not None:  # every pair is routed: the table is complete
@@ -1229,7 +1328,7 @@ def _mkdir_everywhere(group, path):
 
 
 def _demux_ranks(group, args, pairs, results, route_of, table, names, window, level, infix, kind, sheet, lazy,
-                 t_start, report=None, stats=None, cycles=None, bstats=None):
+                 t_start, report=None, stats=None, cycles=None, bstats=None, validate=None):
     import shutil
 
     from .dist import PeerFailed, reduce_min
@@ -1254,6 +1353,8 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                 cycles.begin(dmx, len(names))
             if bstats is not None:
                 bstats.begin(dmx, len(names))
+            if validate is not None:
+                validate.begin(dmx)
             for j, k in enumerate(mine):
                 d = os.path.join(parts, str(k))
                 os.makedirs(d, exist_ok=True)
@@ -1263,7 +1364,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                     if report is not None:
                         report.begin_pair(dmx, k)  # the global pair index: the ordinals are the one-process run's
                     _demux_pair(dmx, pool, gz, 2 * j, 2 * j + 1, pairs[k][0], pairs[k][1], results, route_of, writers,
-                                window, sheet, hit, report, stats, cycles, bstats)
+                                window, sheet, hit, report, stats, cycles, bstats, validate)
                 except (Exception, SystemExit) as e:  # re-raised below if it is the first in pair order
                     failed, exc = k, e
                 finally:

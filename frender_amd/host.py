@@ -250,6 +250,12 @@ def barcode_stats_path(args):
     return path
 
 
+def validate_flag(args) -> bool:
+    """--validate of a demux's arguments (a namespace without the field validates nothing: the reference's
+    namespaces)."""
+    return bool(getattr(args, "validate", False))
+
+
 def gz_format(args) -> str:
     """--gz-format of a demux's arguments (a namespace without it means gzip), checked against --gz-writer:
     only the GPU writer makes BGZF.  Called before anything is opened or created."""

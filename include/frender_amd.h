@@ -528,6 +528,42 @@ int fr_dmx_bstats_window(fr_dmx* d, uint64_t n_pairs);
  * Synchronises. */
 int fr_dmx_bstats_get(fr_dmx* d, int n_dest, uint64_t* out);
 
+/* ---- the demux windows' validation (`demux --validate`; fr_dmx_validate.hip): are a window's record pairs well
+ * formed, and do the mates belong together, checked over the unrouted bytes while they are resident: table mode
+ * and sheet mode alike, and nothing of the route is needed.  A record and its lines are fr_dmx_stats_*'s: fr_dmx_records'
+ * byte span split at its '\n', absent pieces empty.  Pair k is R1's record k with R2's record k; its violation is
+ * the first of these that applies, for R1's record (kinds 1-4), then for R2's (the same four, + 4), then for the
+ * pair:
+ *   TRUNCATED  the span holds fewer than three '\n' (fewer than four lines);
+ *   HEADER     its first byte is not '@';
+ *   SEPARATOR  its third piece is empty or does not start with '+';
+ *   LENGTH     its second piece (sequence) and fourth piece (quality, without the trailing '\n') differ in length;
+ *   NAME       the mates' name tokens differ as bytes: a token is the header line after the '@' up to its first
+ *              space or tab (or its end), without its last two bytes when they are "/1" or "/2";
+ *   CODE       the text after the last ':' of R1's header line (the whole line without a ':') differs from R2's.
+ * The first violation of a window is the one of its lowest pair.  Every call below returns FR_ERR_INVALID, with
+ * nothing queued, when the order described is not kept. */
+#define FR_DMX_V_TRUNCATED 1
+#define FR_DMX_V_HEADER 2
+#define FR_DMX_V_SEPARATOR 3
+#define FR_DMX_V_LENGTH 4
+#define FR_DMX_V_R2 4 /* R2's record kinds are R1's + 4: 5-8 */
+#define FR_DMX_V_NAME 9
+#define FR_DMX_V_CODE 10
+/* Turn the validation on: allocates its result word.  Off, nothing allocated and nothing launched, until this
+ * call. */
+int fr_dmx_validate_begin(fr_dmx* d);
+/* Check the first n_pairs record pairs of the window at hand: after both mates' fr_dmx_load* of the window, once,
+ * before the next fr_dmx_load*; n_pairs is at most each mate's record count.  Queues on the context's stream
+ * (behind the loads, ahead of the fr_dmx_route that follows) and makes no synchronisation of its own. */
+int fr_dmx_validate_window(fr_dmx* d, uint64_t n_pairs);
+/* The last queued window's first violation: *first_pair, relative to the window (-1: none), and *kind (0: none).
+ * Meant to follow that window's fr_dmx_route, whose read-back has waited for the stream already; synchronises
+ * anyway.  FR_ERR_INVALID without a queued window. */
+int fr_dmx_validate_result(fr_dmx* d, int64_t* first_pair, int32_t* kind);
+/* Free the word and turn the validation off (fr_dmx_destroy does as much). */
+int fr_dmx_validate_end(fr_dmx* d);
+
 /* ---- GPU deflate over any byte ranges (fr_deflate.hip; fr_dmx_deflate runs it on the routed bytes).
  * Stream s is bytes [offsets[s], offsets[s + 1]) of the device buffer dev_data (4-byte aligned, 16
  * readable bytes past offsets[n_streams]); every stream becomes one raw deflate stream, no larger than

@@ -20,7 +20,8 @@ flag's cost is the difference) and, with --parent, the parent's `demux -b`, whic
 flag; its output files are compared with the one-pass run's.  With --cycle-stats-arm, `demux -b --cycle-stats` joins
 the rounds in the same way: the flag's cost is its difference to `demux -b` on this tree, and with --parent the
 parent's `demux -b` is timed in the same rounds, which this tree's must equal without the flag.  With
---barcode-stats-arm, `demux -b --barcode-stats` joins the rounds in the same way.  Writes one JSON
+--barcode-stats-arm, `demux -b --barcode-stats` joins the rounds in the same way, and with --validate-arm `demux -b
+--validate`.  Writes one JSON
 document (--out), stamped with the tree's source hash.
 
 Needs a GPU: there is no CPU path to time.
@@ -97,6 +98,9 @@ def main():
     ap.add_argument("--barcode-stats-arm", action="store_true",
                     help="also time demux -b --barcode-stats (the index mismatch table from the same pass) and, with "
                          "--parent, the parent's demux -b in the same rounds")
+    ap.add_argument("--validate-arm", action="store_true",
+                    help="also time demux -b --validate (every pair checked before it is routed, same pass) and, with "
+                         "--parent, the parent's demux -b in the same rounds")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "demux_sheet_bench.json"))
     ap.add_argument("--workdir", help="where the inputs and outputs go (default: a temporary directory)")
     args = ap.parse_args()
@@ -171,6 +175,14 @@ def main():
                          os.path.join(w, "out"), "--stage-times", *allf], w, ROOT)
             return {"total_s": t, "stages": st, "dir": w, "csv": os.path.join(w, "bstats.csv")}
 
+        def validate_pass():
+            serial[0] += 1
+            w = os.path.join(d, f"val_{serial[0]}")
+            os.mkdir(w)
+            t, st = run(["demux", "-b", sheet_csv, "-n", "1", "--validate", "-d", os.path.join(w, "out"), "--stage-times",
+                         *allf], w, ROOT)
+            return {"total_s": t, "stages": st, "dir": w}
+
         def parent_one_pass(root):
             serial[0] += 1
             w = os.path.join(d, f"pone_{serial[0]}")
@@ -222,17 +234,22 @@ def main():
             bstats_doc = {"outputs_equal": digests(os.path.join(cold["bstats"]["dir"], "out")) == db,
                           "csv_rows": len(rows), "csv_reads": sum(int(r["reads"]) for r in rows),
                           "csv_bin_pairs": sorted({f"{r['idx1_mismatches']},{r['idx2_mismatches']}" for r in rows})}
+        validate_doc = None
+        if args.validate_arm:
+            cold["validate"] = validate_pass()
+            validate_doc = {"outputs_equal": digests(os.path.join(cold["validate"]["dir"], "out")) == db}
         csv_path = os.path.join(d, "results.csv")
         shutil.copy(cold["two_pass"]["csv"], csv_path)
         out_files = len(da)
         for c in cold.values():
             shutil.rmtree(c["dir"])
-        warm = {"two_pass": [], "one_pass": [], "report": [], "stats": [], "cycles": [], "bstats": [], "parent_demux_r": [],
+        warm = {"two_pass": [], "one_pass": [], "report": [], "stats": [], "cycles": [], "bstats": [], "validate": [], "parent_demux_r": [],
                 "parent_one_pass": []}
         arms = (("two_pass", two_pass), ("one_pass", one_pass)) + ((("report", report_pass),) if args.report_arm else ()) \
             + ((("stats", stats_pass),) if args.stats_arm else ()) \
             + ((("cycles", cycles_pass),) if args.cycle_stats_arm else ()) \
-            + ((("bstats", bstats_pass),) if args.barcode_stats_arm else ())
+            + ((("bstats", bstats_pass),) if args.barcode_stats_arm else ()) \
+            + ((("validate", validate_pass),) if args.validate_arm else ())
         for _ in range(max(args.runs, 5)):
             for name, fn in arms:
                 r = fn()
@@ -240,7 +257,7 @@ def main():
                 warm[name].append(r)
             if args.parent:
                 warm["parent_demux_r"].append(demux_r(os.path.abspath(args.parent), csv_path))
-                if args.stats_arm or args.cycle_stats_arm or args.barcode_stats_arm:
+                if args.stats_arm or args.cycle_stats_arm or args.barcode_stats_arm or args.validate_arm:
                     warm["parent_one_pass"].append(parent_one_pass(os.path.abspath(args.parent)))
 
         def strip(r):
@@ -329,12 +346,27 @@ def main():
             if warm["parent_one_pass"]:
                 bstats_doc["parent_one_pass_total_s"] = spread([r["total_s"] for r in warm["parent_one_pass"]])
             doc["barcode_stats_arm"] = bstats_doc
+        if validate_doc is not None:
+            val_t = [r["total_s"] for r in warm["validate"]]
+            validate_doc.update({
+                "what": "demux -b -n 1 --validate (every pair checked on the GPU before it is routed, same pass) against "
+                        "demux -b -n 1 on this tree and at the parent commit, in the same alternating rounds",
+                "validate_total_s": spread(val_t),
+                "one_pass_total_s": spread(one_t),
+                "validate_minus_one_pass_s": round(statistics.median(val_t) - statistics.median(one_t), 4),
+                # the kernel is queued behind the loads and waited for with the route's read-back
+                "stages_ms_per_window": {name: {k: per_window_ms([r["stages"] for r in runs], k)
+                                                for k in ("load+index", "route")}
+                                         for name, runs in (("validate", warm["validate"]), ("one_pass", warm["one_pass"]))}})
+            if warm["parent_one_pass"]:
+                validate_doc["parent_one_pass_total_s"] = spread([r["total_s"] for r in warm["parent_one_pass"]])
+            doc["validate_arm"] = validate_doc
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
             f.write("\n")
         print(json.dumps({k: doc[k] for k in ("tree_hash", "outputs_equal", "warm", "stages_ms_per_window", "report_arm",
-                                                   "stats_arm", "cycle_stats_arm", "barcode_stats_arm")
+                                                   "stats_arm", "cycle_stats_arm", "barcode_stats_arm", "validate_arm")
                           if k in doc}))
         if not equal:
             raise SystemExit("the two routes' outputs differ: " +
