@@ -170,10 +170,20 @@ __device__ __forceinline__ u32 gather16p(u32 d0, u32 d1) {
     return v | (u << 8);
 }
 
-// four gather16p quarters -> the segment's 64-bit bitmap; the 2^K scale is undone once per 32-bit half
+// (a << S) | b as one v_lshl_or_b32, whatever the optimizer would make of the expression around it
+template <int S>
+__device__ __forceinline__ u32 lshl_or(u32 a, u32 b) {
+    u32 r;
+    asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "n"(S), "v"(b));
+    return r;
+}
+
+// four gather16p quarters -> the segment's 64-bit bitmap; the 2^K scale is undone once per 32-bit half.
+// Per half: the low quarter's shift (none for K = 0) and one v_lshl_or_b32.  Written as plain shifts and ORs the
+// compiler spreads the shifts over the dot4 results again: two shifts, a v_lshl_or and a v_or3 per half.
 template <int K>
 __device__ __forceinline__ u64 join16p(const u32 (&g)[4]) {
-    const u32 lo = (g[0] >> K) | (g[1] << (16 - K)), hi = (g[2] >> K) | (g[3] << (16 - K));
+    const u32 lo = lshl_or<16 - K>(g[1], g[0] >> K), hi = lshl_or<16 - K>(g[3], g[2] >> K);
     return ((u64)hi << 32) | (u64)lo;
 }
 
@@ -704,7 +714,7 @@ __device__ __forceinline__ bool seg_in_range(const ScanArgs& a, u32 t) {
 }
 
 __device__ __forceinline__ void seg_load(const ScanArgs& a, u32 t, SegRegs& r, int lane) {
-    if (seg_in_range(a, t)) seg_fetch(a, t, r, lane);
+    if (__builtin_expect(seg_in_range(a, t), 1)) seg_fetch(a, t, r, lane);
     else r = seg_load_tail(a, t, lane);
 }
 
@@ -796,7 +806,7 @@ __device__ __forceinline__ SegClass seg_classify_src(const ScanArgs& a, u32 t, c
 #endif
         // bit 4 (byte >= 0x80) exists in classify4's class words only (in a pair word it is a line end)
         u32 hib = 0;
-        if (__ballot(slow) != 0) {  // a wave-uniform SGPR value: a scalar branch
+        if (__builtin_expect(__ballot(slow) != 0, 0)) {  // a wave-uniform SGPR value: a scalar branch
             // a byte >= 0x80 or a fast-table sentinel somewhere in the wave-tile: the exact classifier,
             // out of line on the segment re-read from L2 (no register of the common path is held for it)
             const Cls16 e = classes_exact(a, t, lane);
@@ -807,7 +817,7 @@ __device__ __forceinline__ SegClass seg_classify_src(const ScanArgs& a, u32 t, c
             hib = e.acc & 0x10101010u;
         }
         u64 tm = eol;
-        if (__ballot(cr) != 0) {
+        if (__builtin_expect(__ballot(cr) != 0, 0)) {
             // '\r' somewhere in the wave (CRLF / CR files): a '\r' right before a '\n' ends no line.
             // The segment (and the byte after it) is re-read from L2 here, so no class word has to
             // stay live through the common path.
@@ -823,25 +833,37 @@ __device__ __forceinline__ SegClass seg_classify_src(const ScanArgs& a, u32 t, c
             const u64 nxt = (q.nx & 0xFFu) == (u32)'\n' ? 1ull : 0ull;
             tm = eol & ~(crm & ((nl >> 1) | (nxt << 63)));
         }
-        const u32 bvalid = bl - s0;
-        if (bvalid < SEG) {
-            const u64 vm = (1ull << bvalid) - 1ull;
-            sp &= vm;
-            col &= vm;
-            eol &= vm;
-        }
-        if (s0 < tlen) {
-            const u32 valid = tlen - s0;
-            if (valid < SEG) tm &= (1ull << valid) - 1ull;
+        // a whole wave-tile (uniform; every one but the range's last two): all staged bytes are data and the own
+        // bytes end with lane SEGS - 2's segment, so no lane has a partial mask to build
+        if (__builtin_expect(bl == (u32)TILE && tlen == (u32)TSTEP, 1)) {
+            sc.sp = sp;
+            sc.col = col;
+            sc.eol = eol;
+            if (s0 < (u32)TSTEP) {
+                sc.tmask = tm;
+                sc.hi = hib != 0;
+            }
         } else {
-            tm = 0;
-        }
-        sc.sp = sp;
-        sc.col = col;
-        sc.eol = eol;
-        if (s0 < tlen) {
-            sc.tmask = tm;
-            sc.hi = hib != 0;  // exact own-byte test in drain_rare (kind 4)
+            const u32 bvalid = bl - s0;
+            if (bvalid < SEG) {
+                const u64 vm = (1ull << bvalid) - 1ull;
+                sp &= vm;
+                col &= vm;
+                eol &= vm;
+            }
+            if (s0 < tlen) {
+                const u32 valid = tlen - s0;
+                if (valid < SEG) tm &= (1ull << valid) - 1ull;
+            } else {
+                tm = 0;
+            }
+            sc.sp = sp;
+            sc.col = col;
+            sc.eol = eol;
+            if (s0 < tlen) {
+                sc.tmask = tm;
+                sc.hi = hib != 0;  // exact own-byte test in drain_rare (kind 4)
+            }
         }
     }
     sc.c = __popcll(sc.tmask);
@@ -1433,16 +1455,20 @@ __device__ __forceinline__ bool encode_uniform(const ScanShared& sh, u32 wid, u3
         const u32 x = __builtin_amdgcn_alignbyte(w[k + 1], w[k], al);
         const u32 idx = (x >> 1) & 0x07070707u;
         const u32 expect = __builtin_amdgcn_perm(0x4E002B00u, 0x47544341u, idx);
-        u32 sym = __builtin_amdgcn_perm(0x05000600u, 0x03040201u, idx);
+        const u32 sym = __builtin_amdgcn_perm(0x05000600u, 0x03040201u, idx);
         const u32 left = nu - 4u * k;
+        // each arm computes packed itself (a sym masked in one arm only made the compiler copy it in the other)
+        u32 packed;
         if (left >= 4u) {
-            bad |= expect ^ x;
+            bad = __builtin_amdgcn_bitop3_b32(expect, x, bad, 0xBEu);  // (expect ^ x) | bad in one op
+            packed = __builtin_amdgcn_udot4(sym, 0x00400801u, (sym >> 15) & 0xE00u, false);
         } else {
             const u32 vm = 0xFFFFFFFFu >> (32u - 8u * left);  // uniform
             bad |= (expect ^ x) & vm;
-            sym &= vm;
+            const u32 sv = sym & vm;
+            // no fourth byte, so no term from above the dot4's 8-bit weights; a single byte is its own symbol
+            packed = left == 1u ? sv : __builtin_amdgcn_udot4(sv, 0x00400801u, 0u, false);
         }
-        const u32 packed = __builtin_amdgcn_udot4(sym, 0x00400801u, (sym >> 15) & 0xE00u, false);
         if (k == 0) lo = packed;
         else if (k == 1) lo |= packed << 12;
         else if (k == 2) { lo |= packed << 24; hi = packed >> 8; }
@@ -1460,7 +1486,9 @@ __device__ __forceinline__ bool encode_uniform(const ScanShared& sh, u32 wid, u3
 // staged bytes, or no ' ' / line end within 64 bytes); 3 the token ends past the window (a first token of
 // 40-odd bytes: Illumina instrument headers), which locate_code finishes from the token start.
 __device__ __forceinline__ int locate_near(const ScanShared& sh, u32 wid, u32 p, u32 bl, u32& start, u32& n, u32& f1) {
-    const u32 w = min(p >> 6, (u32)SEGS - 1u), b = p & 63u;
+    // p <= TILE (a segment's last byte ends the line before it), so word w <= SEGS and w + 1 lie inside the
+    // SEGS + 2 words without a clamp; p == TILE is past the staged bytes and returns 2 whatever the window holds
+    const u32 w = p >> 6, b = p & 63u;
     const lds_u64* S = (const lds_u64*)&sh.bsp[wid][w];
     const lds_u64* C = (const lds_u64*)&sh.bcol[wid][w];
     u64 s0 = S[0], s1 = S[1], c0 = C[0], c1 = C[1];
@@ -1481,7 +1509,7 @@ __device__ __forceinline__ void parse_header(ScanShared& sh, const ScanArgs& a, 
                                              const ColdDest& cd, ColdPend& pd) {
     u32 start = 0, n = 0, f1 = 0;
     int r = locate_near(sh, wid, p, bl, start, n, f1);
-    if (__ballot(r == 3) != 0) {  // uniform: some lane's token ends past its first window
+    if (__builtin_expect(__ballot(r == 3) != 0, 0)) {  // uniform: some lane's token ends past its first window
         if (r == 3) {
             r = locate_code(sh, wid, p, bl, start, n);  // decides "no ' '" itself
             f1 = 0xFFFFFFFFu;
@@ -1529,12 +1557,19 @@ __device__ __forceinline__ void parse_own_headers(ScanShared& sh, const ScanArgs
     const u32 lb = (u32)L0 + (sc.x - sc.c);  // terminators before this segment (low bits)
     const u32 skip = (3u - lb) & 3u;
     const u32 s0 = lane * SEG;
-    u64 m = sc.tmask;
+    // The skip-th terminator of the segment (skip <= 3), in 32 bits: the half that holds it follows from the low
+    // half's popcount (sc.c's first v_bcnt), then up to three lowest bits of that half are cleared, each by one
+    // compare, one subtract with borrow and one AND.  (It was three rounds on the 64-bit mask: a 64-bit add, a
+    // compare, two selects and two ANDs each, then a 64-bit ctz, a 64-bit test and a 64-bit popcount.)
+    const u32 tlo = (u32)sc.tmask, thi = (u32)(sc.tmask >> 32);
+    const u32 clo = __popc(tlo);
+    const bool in_lo = skip < clo;
+    u32 hx = in_lo ? tlo : thi;
+    const u32 hk = in_lo ? skip : skip - clo;
 #pragma unroll
-    for (u32 q = 0; q < 3; ++q) {
-        const u64 d = m & (m - 1ull);
-        m = q < skip ? d : m;
-    }
+    for (u32 q = 0; q < 3; ++q) hx &= hx - (q < hk ? 1u : 0u);
+    const bool have = sc.c > skip;              // the segment holds a header terminator
+    const u32 hpos = ffbl32(hx) + (in_lo ? 0u : 32u);  // its bit (have)
     constexpr bool limited = LIM;  // -s (a.max_records > 0): the kernel instance's, so the common one has no record limit
     u64 rec = 0;
     if (limited) rec = (L0 + (sc.x - sc.c) + skip + 1u) >> 2;
@@ -1542,13 +1577,20 @@ __device__ __forceinline__ void parse_own_headers(ScanShared& sh, const ScanArgs
     const bool own0s = t == 0 && a.own_start && (L0 & 3ull) == 0 && a.avail > 0 &&
                        (!limited || (i64)(L0 >> 2) < a.max_records);
     const bool own0 = own0s && lane == 0;
-    // m's lowest set bit: the first header terminator.  own0's header at position 0 comes first.
-    const u32 p = own0 ? 0u : s0 + ctz64x(m) + 1u;
-    const bool ok = own0 || (m != 0 && p < pend && (!limited || (i64)rec < a.max_records));
+    // the first header terminator.  own0's header at position 0 comes first.
+    const u32 p = own0 ? 0u : s0 + hpos + 1u;
+    const bool ok = own0 || (have && p < pend && (!limited || (i64)rec < a.max_records));
     if (ok) parse_header(sh, a, wid, tile0c, p, bl, cd, pd);
     // another header in this segment (records shorter than 64 B; never at R=8's 74 B): uniform check
-    bool more = ok && (own0 ? m != 0 : __popcll(m) > 4);
-    if (!__ballot(more)) return;
+    bool more = ok && (own0 ? have : sc.c > skip + 4u);
+    if (__builtin_expect(!__ballot(more), 1)) return;
+    // the terminator mask from the first header terminator on (in 64 bits, for the loop below)
+    u64 m = sc.tmask;
+#pragma unroll
+    for (u32 q = 0; q < 3; ++q) {
+        const u64 d = m & (m - 1ull);
+        m = q < skip ? d : m;
+    }
     if (!own0) {
         m &= m - 1ull;
         m &= m - 1ull;
@@ -1578,6 +1620,11 @@ __device__ __forceinline__ void parse_own_headers(ScanShared& sh, const ScanArgs
 // next tile's loads at once and those stay in flight through this tile's classify AND its parse;
 // the classify reads the lane's segment back from LDS.  A lane's LDS-table miss of tile t waits in registers (pd)
 // and is stored to the cold list at the top of step t + 1, ahead of that step's loads, or after the loop.
+// The loop's rare branches (seg_load_tail, classes_exact, the '\r' re-read, drain_rare, locate_code, a second header
+// in a segment) are marked unlikely: the out-of-line calls among them clobber every caller-saved SGPR, and with
+// the branches weighted evenly the register allocator kept the walk's uniforms (the buffer descriptor, ColdDest,
+// te, ct, the range-end flags) in spill lanes and reloaded them with v_readlane / v_writelane on the path every
+// tile takes; now the saves and reloads sit in the rare blocks, around the calls.
 template <bool LIM>
 __device__ __forceinline__ u64 walk_wave(ScanShared& sh, const ScanArgs& a0, u32 ct, u32 tb, u32 te, u64 L0,
                                          bool parse, int lane, u32 wid) {
@@ -1619,7 +1666,7 @@ __device__ __forceinline__ u64 walk_wave(ScanShared& sh, const ScanArgs& a0, u32
         if (sc.hi) rare_push(sh, a, (t - ct) * TSTEP + lane * SEG, 4u,
                              min((u32)min((u64)TSTEP, a.len - (u64)t * TSTEP) - lane * SEG, (u32)SEG), 0u);
         const u32 tail = *(const volatile lds_u32*)&sh.rq_tail[wid];
-        if (tail != done) {  // uniform: the previous tile's rare events (and this tile's UTF-8 checks)
+        if (__builtin_expect(tail != done, 0)) {  // uniform: the previous tile's rare events (and this tile's UTF-8 checks)
             drain_rare(sh, a, wid, done, tail, lane);
             done = tail;
         }
