@@ -123,6 +123,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "(independent members of at most 64 KiB each and an EOF block, as bgzip writes: readable "
                         "by bgzip/htslib tools, by this project's member-parallel readers and by scan "
                         "--gz-reader gpu; 1.4-2.0 %% larger; needs --gz-writer gpu)")
+    d.add_argument("--gz-reader", choices=("host", "gpu"), default="host",
+                   help="who inflates the inputs: host (default: the native inflate pool) or gpu (an input that is BGZF "
+                        "as bgzip or --gz-format bgzf writes it goes to the GPU compressed and is decoded there, window "
+                        "by window, in the buffer it is routed from; any other input, and one whose text is not plain "
+                        "ASCII without '\\r', is read on the host as ever; same outputs; works with --gpus)")
     d.add_argument("--gpus", type=int, default=1,
                    help="GPUs (one process each; file pairs are dealt to them, rank 0 writes the outputs)")
     d.add_argument("--single-index", action="store_true",

@@ -185,6 +185,12 @@ _SIGS = {
     "fr_dmx_validate_window": (C.c_int, [P, C.c_uint64]),
     "fr_dmx_validate_result": (C.c_int, [P, P, P]),
     "fr_dmx_validate_end": (C.c_int, [P]),
+    "fr_dmx_bgzf_open": (C.c_int, [P, C.c_int, C.c_char_p, C.c_uint64, C.POINTER(C.c_int)]),
+    "fr_dmx_bgzf_fill": (C.c_int, [P, C.c_int, C.c_uint64, C.c_uint64, u64p, u64p, C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int), u64p]),
+    "fr_dmx_bgzf_close": (C.c_int, [P, C.c_int]),
+    "fr_dmx_bgzf_info": (C.c_int, [P, C.c_int, C.POINTER(C.c_double)]),
+    "fr_dmx_window_read": (C.c_int, [P, C.c_int, C.c_uint64, C.c_uint64, P]),
     "fr_defl_create": (P, [C.c_int]),
     "fr_defl_destroy": (None, [P]),
     "fr_defl_last_error": (C.c_char_p, [P]),
@@ -552,6 +558,37 @@ class Demux:
         n = C.c_uint64()
         self._ck(lib.fr_dmx_load_device(self.h, mate, P(dev_ptr), nbytes, C.byref(n)), "fr_dmx_load_device")
         return n.value
+
+    BGZF_INFO = ("files", "members", "fills", "handovers", "handover_fill", "inflate_ms", "text_ms", "bytes")
+
+    def bgzf_open(self, mate: int, path, chunk_bytes: int = 0) -> bool:
+        """fr_dmx_bgzf_open: True when the GPU reader takes the file as the mate's."""
+        taken = C.c_int()
+        self._ck(lib.fr_dmx_bgzf_open(self.h, mate, os.fsencode(str(path)), int(chunk_bytes), C.byref(taken)),
+                 "fr_dmx_bgzf_open")
+        return bool(taken.value)
+
+    def bgzf_fill(self, mate: int, keep_from: int, want: int) -> tuple:
+        """fr_dmx_bgzf_fill -> (n_records, len, eof, handed_over, resume)."""
+        n, ln, res = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        eof, hand = C.c_int(), C.c_int()
+        self._ck(lib.fr_dmx_bgzf_fill(self.h, mate, int(keep_from), int(want), C.byref(n), C.byref(ln), C.byref(eof),
+                                      C.byref(hand), C.byref(res)), "fr_dmx_bgzf_fill")
+        return n.value, ln.value, bool(eof.value), bool(hand.value), res.value
+
+    def bgzf_close(self, mate: int):
+        self._ck(lib.fr_dmx_bgzf_close(self.h, mate), "fr_dmx_bgzf_close")
+
+    def bgzf_info(self, mate: int) -> dict:
+        out = (C.c_double * 8)()
+        self._ck(lib.fr_dmx_bgzf_info(self.h, mate, out), "fr_dmx_bgzf_info")
+        return dict(zip(self.BGZF_INFO, (float(v) for v in out)))
+
+    def window_read(self, mate: int, start: int, end: int) -> bytes:
+        """Bytes [start, end) of the mate's window at hand (fr_dmx_window_read)."""
+        out = np.empty(max(int(end) - int(start), 0), np.uint8)
+        self._ck(lib.fr_dmx_window_read(self.h, mate, int(start), int(end), _ptr(out)), "fr_dmx_window_read")
+        return out.tobytes()
 
     def records(self, mate: int, recs) -> tuple:
         r = np.ascontiguousarray(recs, dtype=np.uint64)

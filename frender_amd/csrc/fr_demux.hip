@@ -439,6 +439,8 @@ struct fr_dmx {
     DmxValidate* validate = nullptr;
     bool vloaded[2] = {false, false};
     bool vqueued = false;
+    // the GPU reader of BGZF mates (fr_dmx_bgzf_open; fr_dmx_reader.hip): never created without that call
+    DmxReader* reader = nullptr;
 };
 
 #define DK(x)                                                                  \
@@ -487,6 +489,7 @@ void fr_dmx_destroy(fr_dmx* d) {
     dmx_cycles_destroy(d->cycles);
     dmx_bstats_destroy(d->bstats);
     dmx_validate_destroy(d->validate);
+    dmx_reader_destroy(d->reader);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
 }
@@ -978,6 +981,54 @@ int fr_dmx_validate_end(fr_dmx* d) {
     dmx_validate_destroy(d->validate);  // (waits for the stream: a queued window still writes the word)
     d->validate = nullptr;
     d->vqueued = false;
+    return FR_OK;
+}
+
+// ---- the GPU reader of BGZF mates: the arguments are checked here and a filled window is indexed here, the
+// files, the staging and the window buffers are fr_dmx_reader.hip's
+int fr_dmx_bgzf_open(fr_dmx* d, int mate, const char* path, uint64_t chunk_bytes, int* taken) {
+    if (mate < 0 || mate > 1 || !taken) return d->err = "fr_dmx_bgzf_open: mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    return dmx_reader_open(&d->reader, d->device, d->stream, mate, path, chunk_bytes, taken, d->err);
+}
+
+int fr_dmx_bgzf_fill(fr_dmx* d, int mate, uint64_t keep_from, uint64_t want, uint64_t* n_records, uint64_t* len,
+                     int* eof, int* handed_over, uint64_t* resume) {
+    if (mate < 0 || mate > 1 || !dmx_reader_is_open(d->reader, mate))
+        return d->err = "fr_dmx_bgzf_fill: no file is open for the mate (fr_dmx_bgzf_open)", FR_ERR_INVALID;
+    const u8* win = nullptr;
+    *n_records = 0;
+    if (int rc = dmx_reader_fill(d->reader, mate, keep_from, want, &win, len, eof, handed_over, resume, d->err))
+        return rc;
+    if (*handed_over) {  // the carry alone, for fr_dmx_window_read: no records until the host loads its window
+        d->src[mate] = win;
+        d->len[mate] = *len;
+        d->nrec[mate] = 0;
+        d->routed_ok = d->stats_ok = d->cycles_ok = d->bstats_ok = 0;
+        d->vloaded[mate] = false;
+        if (mate == 1) d->rbin_loaded = false;
+        return FR_OK;
+    }
+    return dmx_index_mate(d, mate, win, *len, n_records);
+}
+
+int fr_dmx_bgzf_close(fr_dmx* d, int mate) {
+    if (mate < 0 || mate > 1) return d->err = "fr_dmx_bgzf_close: mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    dmx_reader_close(d->reader, mate);
+    return FR_OK;
+}
+
+int fr_dmx_bgzf_info(fr_dmx* d, int mate, double out[8]) {
+    if (mate < 0 || mate > 1 || !out) return d->err = "fr_dmx_bgzf_info: mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    dmx_reader_info(d->reader, mate, out);
+    return FR_OK;
+}
+
+int fr_dmx_window_read(fr_dmx* d, int mate, uint64_t start, uint64_t end, uint8_t* out) {
+    if (mate < 0 || mate > 1) return d->err = "fr_dmx_window_read: mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    if (start > end || end > d->len[mate] || (end > start && !d->src[mate]))
+        return d->err = "fr_dmx_window_read: the span is not inside the mate's window", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    if (end > start) DK(hipMemcpy(out, d->src[mate] + start, end - start, hipMemcpyDeviceToHost));
     return FR_OK;
 }
 

@@ -240,6 +240,12 @@ static int run_device(fr_infl* z, const uint8_t* dev_in, const uint64_t* in_off,
 
 namespace fr {
 
+// run_device for the other readers of this library (fr_dmx_reader.hip): fr_infl_run with the choice of `pairs`
+int infl_run(fr_infl* z, const uint8_t* dev_in, const uint64_t* in_off, uint8_t* dev_out, const uint64_t* out_off, int n,
+             uint8_t* status, uint32_t* crc32, int pairs) {
+    return run_device(z, dev_in, in_off, dev_out, out_off, n, status, crc32, pairs);
+}
+
 // A whole BGZF file through the context: *ok = 1 with the decoded bytes on the device (16-byte aligned,
 // 16 zero bytes past the end, valid until the context's next run) when every member decoded to its
 // trailer's size and CRC-32; *ok = 0 when the file is not one the GPU reader takes or a member failed.

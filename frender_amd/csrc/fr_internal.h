@@ -10,6 +10,7 @@
 #include <vector>
 
 struct fr_ctx;
+struct fr_infl;
 
 namespace fr {
 
@@ -400,6 +401,11 @@ constexpr u64 BGZF_MAX_IN = 1ull << 30;  // compressed bytes of a BGZF file for 
 // fr_gz.cpp: the host path's member walk (bgzf_members) and size budget, and as fr_bgzf_probe's walk the
 // extra field must be the BC subfield alone (XLEN 6); false: not such a file
 bool bgzf_member_table(const u8* data, size_t n, std::vector<BgzfMember>& out);
+// fr_inflate.hip: fr_infl_run with the stream list's form chosen: pairs = 1, stream s is [in_off[2s], in_off[2s + 1])
+// of dev_in (a BGZF piece's members, headers and trailers between them), else [in_off[s], in_off[s + 1]).  The bytes
+// are decoded, and the stream idle, when it returns
+int infl_run(::fr_infl* z, const u8* dev_in, const u64* in_off, u8* dev_out, const u64* out_off, int n, u8* status,
+             u32* crc32, int pairs);
 // fr_deflate.hip: the operator "feed n zero bytes into the raw CRC-32 register", byte-sliced (4 x 256 words)
 void crc_shift_table(u64 n, u32* T);
 // fr_api.hip, for fr_dmx_set_sheet: the device sheet of ctx and its neighbourhood maps for (nsubs1, nsubs2)
@@ -464,5 +470,19 @@ void dmx_validate_destroy(DmxValidate* t);
 int dmx_validate_window(DmxValidate* t, const u8* b1, const u8* b2, const u64* rs1, const u64* rs2, u64 n,
                         std::string& err);
 int dmx_validate_result(DmxValidate* t, int64_t* first_pair, int32_t* kind, std::string& err);
+
+// ---- the demux windows' GPU reader (fr_dmx_reader.hip: `demux --gz-reader gpu`; fr_demux.hip's fr_dmx_bgzf_* entry
+// points check the arguments, forward here and index the window a fill returns).  A mate's BGZF file is decoded
+// window by window into one of two device buffers of the reader's own; see include/frender_amd.h for the contract.
+struct DmxReader;
+int dmx_reader_open(DmxReader** r, int device, hipStream_t stream, int mate, const char* path, u64 chunk_bytes,
+                    int* taken, std::string& err);
+// *win, *len: the mate's new window (16-byte aligned, 16 addressable bytes past len); on a hand-over the carry alone
+int dmx_reader_fill(DmxReader* r, int mate, u64 keep_from, u64 want, const u8** win, u64* len, int* eof,
+                    int* handed_over, u64* resume, std::string& err);
+bool dmx_reader_is_open(const DmxReader* r, int mate);
+void dmx_reader_close(DmxReader* r, int mate);
+void dmx_reader_destroy(DmxReader* r);
+void dmx_reader_info(const DmxReader* r, int mate, double out[8]);
 
 }  // namespace fr

@@ -43,8 +43,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from .host import (barcode_stats_path, cycle_stats_path, demux_mode, get_indexes, gz_format, input_spec, limits_of, mismatch_limits,
-                   num_subs_of, parse_files, report_args, single_index, stats_path, validate_flag)
+from .host import (barcode_stats_path, cycle_stats_path, demux_mode, get_indexes, gz_format, gz_reader, input_spec, limits_of,
+                   mismatch_limits, num_subs_of, parse_files, report_args, single_index, stats_path, validate_flag)
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
 # the column order `scan` itself writes (frender.py:482-501, report_analysis)
@@ -393,12 +393,201 @@ def _span(parts, start: int, end: int) -> bytes:
     return b"".join(out)
 
 
-def _code_at(bufs, start: int) -> str:
-    """The code of the R2 record whose header line starts at byte `start` of R2's window (frender.py:778)."""
-    return _line_at(bufs[1], start).split(b":")[-1].decode("utf-8")
+def _code_of(line: bytes) -> str:
+    """The code of the R2 record whose header line is `line` (frender.py:778)."""
+    return line.split(b":")[-1].decode("utf-8")
+
+
+def _skip_bytes(chunks, n: int):
+    """The chunks of an iterator of bytes without their first n bytes."""
+    for c in chunks:
+        if n >= len(c):
+            n -= len(c)
+            continue
+        yield c[n:] if n else c
+        n = 0
+
+
+class _HostWindow:
+    """A mate's window on the host: a list of decoded blocks (never joined here) read from the mate's text_chunks
+    stream, loaded to the GPU with load_parts.  One of the two implementations of a mate's window in _demux_pair:
+    read(window) fills it to `window` bytes, load(dmx) -> its records, span / line_at give its bytes, carry(start)
+    keeps the bytes from `start` on for the next window (None: nothing), has_more() -- after the last carry --
+    says whether the mate holds a byte past the routed records or its stream yields one more, close() ends it."""
+
+    def __init__(self, mate: int, stream, parts=None):
+        self.mate, self.stream = mate, stream
+        self.parts = list(parts or [])
+        self.eof = False
+
+    def read(self, window: int):
+        size = sum(len(p) for p in self.parts)
+        while size < window and not self.eof:
+            try:
+                c = next(self.stream)
+            except StopIteration:
+                self.eof = True
+                break
+            self.parts.append(c)
+            size += len(c)
+
+    def load(self, dmx, window: int) -> int:
+        return dmx.load_parts(self.mate, self.parts)
+
+    def span(self, dmx, start: int, end: int) -> bytes:
+        return _span(self.parts, start, end)
+
+    def line_at(self, dmx, start: int) -> bytes:
+        return _line_at(self.parts, start)
+
+    def lines_at(self, dmx, starts) -> list:
+        return [_line_at(self.parts, s) for s in starts]
+
+    def carry(self, start):
+        self.parts = [] if start is None else _tail(self.parts, start)
+
+    def has_more(self, dmx) -> bool:
+        return any(len(p) for p in self.parts) or (not self.eof and next(self.stream, None) is not None)
+
+    def close(self):
+        self.stream.close()
+
+
+FETCH_WINDOW_FROM = 64  # lines_at of a device window: from this many lines on, the whole window in one copy (DMX_BATCH)
+
+
+class _DeviceWindow:
+    """A mate's window in HBM, filled by the GPU reader (Demux.bgzf_fill: `--gz-reader gpu`, a BGZF mate): the same
+    interface as _HostWindow's, the bytes fetched only where the host needs them (Demux.window_read).  When the reader
+    hands the file over, this window becomes a _HostWindow whose first part is the carry and whose stream is the
+    file's text_chunks from the decoded offset on, inflated by a pool of its own with the session's threads; from
+    then on every call is that window's."""
+
+    def __init__(self, mate: int, path, threads: int):
+        self.mate, self.path, self.threads = mate, path, threads
+        self.keep = 0      # offset in the window at hand of the first byte the next one keeps
+        self.len = 0
+        self.eof = False
+        self.host = None   # the _HostWindow after a hand-over
+        self.pool = None
+        self.cache = None  # the whole window's bytes, once fetched
+
+    def read(self, window: int):
+        if self.host is not None:
+            self.host.read(window)
+
+    def _hand_over(self, dmx, resume: int):
+        carry = dmx.window_read(self.mate, 0, self.len) if self.len else b""
+        dmx.bgzf_close(self.mate)
+        self.pool = _lib.GzPool([str(self.path)], threads=self.threads, ahead=1)
+        self.host = _HostWindow(self.mate, _skip_bytes(text_chunks(self.path, self.pool, 0), resume),
+                                [carry] if carry else [])
+
+    def load(self, dmx, window: int) -> int:
+        if self.host is None:
+            t0 = time.perf_counter()
+            n, self.len, self.eof, handed, resume = dmx.bgzf_fill(self.mate, self.keep, window)
+            info = dmx.bgzf_info(self.mate)  # the fill's kernels, beside the wall time of the whole call
+            for key, v in (("device fill", time.perf_counter() - t0), ("device fill: inflate kernel", info["inflate_ms"] / 1e3),
+                           ("device fill: text kernel", info["text_ms"] / 1e3)):
+                STAGE_TIMES[key] = STAGE_TIMES.get(key, 0.0) + v
+            self.keep, self.cache = 0, None
+            if not handed:
+                return n
+            self._hand_over(dmx, resume)
+            self.host.read(window)
+        return self.host.load(dmx, window)
+
+    def span(self, dmx, start: int, end: int) -> bytes:
+        if self.host is not None:
+            return self.host.span(dmx, start, end)
+        if self.cache is not None:
+            return self.cache[start:end]
+        return dmx.window_read(self.mate, min(start, self.len), min(end, self.len))
+
+    def line_at(self, dmx, start: int) -> bytes:
+        if self.host is not None:
+            return self.host.line_at(dmx, start)
+        if self.cache is not None:
+            e = self.cache.find(b"\n", start)
+            return self.cache[start:e if e >= 0 else self.len]
+        step, out = 512, []
+        while start < self.len:  # headers are short: one copy as a rule
+            c = dmx.window_read(self.mate, start, min(start + step, self.len))
+            e = c.find(b"\n")
+            if e >= 0:
+                out.append(c[:e])
+                break
+            out.append(c)
+            start += len(c)
+            step *= 8
+        return b"".join(out)
+
+    def lines_at(self, dmx, starts) -> list:
+        if self.host is None and self.cache is None and len(starts) >= FETCH_WINDOW_FROM:
+            self.cache = dmx.window_read(self.mate, 0, self.len)  # a window of exotic codes: one copy, not one each
+        return [self.line_at(dmx, s) for s in starts]
+
+    def carry(self, start):
+        if self.host is not None:
+            return self.host.carry(start)
+        self.keep = self.len if start is None else start
+
+    def has_more(self, dmx) -> bool:
+        if self.host is None:
+            if self.keep < self.len:
+                return True
+            if self.eof:
+                return False
+            self.load(dmx, 1)  # past the empty members, if that is all there is (or to a hand-over)
+            if self.host is None:
+                return self.len > 0
+        return self.host.has_more(dmx)
+
+    def close(self):
+        if self.host is not None:
+            self.host.close()
+        if self.pool is not None:
+            self.pool.close()
+            self.pool = None
+
+
+class GpuReader:
+    """`demux --gz-reader gpu` for one session: which of its input files the host pool leaves to the GPU reader --
+    those whose first member header is plain BGZF's, what fr_dmx_bgzf_open checks too -- and a mate's window for
+    either kind.  threads: the session's inflate threads, for the files handed over."""
+    HEAD = b"\x1f\x8b\x08\x04"
+
+    def __init__(self, paths, threads: int, chunk_bytes: int = 0):
+        self.threads, self.chunk_bytes = threads, int(chunk_bytes)
+        self.pool_index, self.pool_paths = {}, []  # position in `paths` -> file of the host pool
+        for i, p in enumerate(paths):
+            if not self.looks_taken(p):
+                self.pool_index[i] = len(self.pool_paths)
+                self.pool_paths.append(p)
+
+    @classmethod
+    def looks_taken(cls, path) -> bool:
+        try:
+            with open(path, "rb") as f:
+                h = f.read(18)
+                return (len(h) == 18 and h[:4] == cls.HEAD and h[10:16] == b"\x06\x00BC\x02\x00"
+                        and h[16] + 256 * h[17] + 1 >= 26 and os.fstat(f.fileno()).st_size >= 26)
+        except OSError:
+            return False
+
+    def window(self, dmx, mate: int, path, gz, i: int):
+        """The window of the file at position i of the session's paths, as mate `mate`."""
+        if i in self.pool_index:
+            return _HostWindow(mate, text_chunks(path, gz, self.pool_index[i]))
+        w = _DeviceWindow(mate, path, self.threads)
+        if not dmx.bgzf_open(mate, path, self.chunk_bytes):  # the library declines after all: the host reader's
+            w._hand_over(dmx, 0)
+        return w
 
 
 STAGE_TIMES = {}  # seconds per stage of _demux_pair's windows (demux --stage-times prints them)
+READER_INFO = {}  # --gz-reader gpu: the reader's counters per mate after the last pair (printed with the stage times)
 
 
 def plan_destinations(ids, samples: bool, undeter: bool, index_hop: bool, ambiguous: bool):
@@ -984,7 +1173,7 @@ class Validate:
 
 
 def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of, writers, window, sheet=None,
-                hit=None, report=None, stats=None, cycles=None, bstats=None, validate=None):
+                hit=None, report=None, stats=None, cycles=None, bstats=None, validate=None, reader=None):
     """One R1/R2 pair in record-aligned windows: the GPU indexes both windows, the complete
     record pairs are routed, and the bytes after the last routed record carry into the next
     window.  Pairing stops when either mate runs out of records (zip, frender.py:777).  The mates
@@ -995,29 +1184,31 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
     after its begin, with sheet): `--barcode-stats`, every routed window is counted per mismatch bin pair; validate
     (Validate, after its begin): `--validate`, every window's pairs are checked before they are routed, the earlier of
     the first bad pair and the route's first error is raised (the bad pair at a tie: a malformed record's code means
-    nothing), and at the end neither mate may have a record left."""
+    nothing), and at the end neither mate may have a record left.  reader (GpuReader): `--gz-reader gpu`, i1 and i2
+    are positions in its paths and a BGZF mate's windows are filled on the device."""
     mates = [os.path.basename(str(read1_file)), os.path.basename(str(read2_file))]
     n_routed = 0  # pairs routed so far: --validate's record numbers count from the file pair's first
-    streams =[text_chunks(read1_file, gz, i1), text_chunks(read2_file, gz, i2)]
-    bufs = [[], []]  # each mate's window as a list of decoded blocks (never joined on the host)
-    eof = [False, False]
+    if reader is None:
+        wins_in = [_HostWindow(0, text_chunks(read1_file, gz, i1)), _HostWindow(1, text_chunks(read2_file, gz, i2))]
+    else:
+        wins_in = []
+        try:
+            for m, (f, i) in enumerate(((read1_file, i1), (read2_file, i2))):
+                wins_in.append(reader.window(dmx, m, f, gz, i))
+        except BaseException:
+            for w in wins_in:
+                w.close()
+            raise
     pending = []  # the previous window's gzip jobs: overlap with this window's inflate and GPU work
     st, clock = STAGE_TIMES, time.perf_counter
     try:
         while True:
             t0 = clock()
-            for m in (0, 1):
-                size = sum(len(p) for p in bufs[m])
-                while size < window and not eof[m]:
-                    try:
-                        c = next(streams[m])
-                    except StopIteration:
-                        eof[m] = True
-                        break
-                    bufs[m].append(c)
-                    size += len(c)
+            for w in wins_in:
+                w.read(window)
             t1 = clock()
-            n = [dmx.load_parts(0, bufs[0]), dmx.load_parts(1, bufs[1])]
+            n = [wins_in[0].load(dmx, window), wins_in[1].load(dmx, window)]
+            eof = [w.host.eof if getattr(w, "host", None) is not None else w.eof for w in wins_in]
             t2 = clock()
             # the last record of a window may continue in the next one unless its file ended
             done = [n[m] if eof[m] else max(n[m] - 1, 0) for m in (0, 1)]
@@ -1033,7 +1224,7 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
             codes = []
             if ex.size:  # codes outside the fast alphabet: resolve by string
                 starts, _ = dmx.records(1, ex)
-                codes = [_code_at(bufs, s) for s in starts.tolist()]
+                codes = [_code_of(ln) for ln in wins_in[1].lines_at(dmx, starts.tolist())]
                 dest = sheet.resolve(codes) if sheet is not None else \
                     [route_of(results[c]) if c in results else _lib.FR_DMX_MISSING for c in codes]
                 dmx.patch(ex, np.array(dest, dtype=np.int32))
@@ -1044,11 +1235,11 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
             if validate is not None:
                 bad, kind = validate.result(dmx)
                 if bad >= 0 and (first < 0 or bad <= first):  # the earlier pair; at the same pair the validation
-                    recs = [_span(bufs[m], *(int(v[0]) for v in dmx.records(m, [bad]))) for m in (0, 1)]
+                    recs = [wins_in[m].span(dmx, *(int(v[0]) for v in dmx.records(m, [bad]))) for m in (0, 1)]
                     raise SystemExit(Validate.message(*mates, n_routed + bad + 1, kind, *recs))
             if first >= 0:
                 s, _ = dmx.records(1, [first])
-                code = _code_at(bufs, int(s[0]))
+                code = _code_of(wins_in[1].line_at(dmx, int(s[0])))
                 if val == _lib.FR_DMX_MISSING:
                     raise SystemExit(f"Couldn't find barcode {code} in supplied frender result file!")
                 err = sheet.error(code, val) if sheet is not None else None
@@ -1087,21 +1278,24 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
             for m in (0, 1):
                 if n_pairs < n[m]:
                     s, _ = dmx.records(m, [n_pairs])
-                    bufs[m] = _tail(bufs[m], int(s[0]))
+                    wins_in[m].carry(int(s[0]))
                 else:
-                    bufs[m] = []
+                    wins_in[m].carry(None)
             if (eof[0] and n_pairs == n[0]) or (eof[1] and n_pairs == n[1]):
                 break
         if validate is not None:
             # a mate has a record left if it holds a byte past the routed records, or its stream yields one more
-            more = [any(len(p) for p in bufs[m]) or (not eof[m] and next(streams[m], None) is not None) for m in (0, 1)]
+            more = [w.has_more(dmx) for w in wins_in]
             if more[0] != more[1]:
                 raise SystemExit(Validate.message(*mates, n_routed + 1, V_COUNT, left=1 if more[0] else 2))
     finally:
         for j in pending:
             j.result()
-        for st in streams:
-            st.close()
+        for w in wins_in:
+            w.close()
+        if reader is not None:
+            for m in (0, 1):
+                dmx.bgzf_close(m)
 
 
 def _drop_unhit(names, lazy, hit, out_dir, infix) -> None:
@@ -1123,8 +1317,11 @@ def _close_writers(writers, names, lazy, hit, out_dir, infix) -> None:
 
 
 @contextlib.contextmanager
-def _session(t_start, paths, kind, n_dest, device, sheet, table, dev=None, ctx=None, finish=None):
-    """What one process demultiplexes with, on one GPU or as a rank of N: (dmx, pool, gz).  gz, the inflate
+def _session(t_start, paths, kind, n_dest, device, sheet, table, dev=None, ctx=None, finish=None, gz_reader="host",
+             reader_chunk=0):
+    """What one process demultiplexes with, on one GPU or as a rank of N: (dmx, pool, gz, reader).  reader is None
+    unless gz_reader is "gpu": then a GpuReader over `paths`, and gz holds only the files that one leaves to the
+    host (None when it leaves none), so no host thread inflates a file the GPU reader takes.  gz, the inflate
     pool over `paths`, comes first: with the GPU compressing, the host's cores inflate (a big single-member
     file in parallel), and its workers start at once, so the first blocks decode while the device context
     comes up.  dmx is the caller's `dev` or a Demux of `device`, bound to the sheet (on the caller's `ctx`, if
@@ -1135,7 +1332,11 @@ def _session(t_start, paths, kind, n_dest, device, sheet, table, dev=None, ctx=N
     gz = dmx = pool = None
     try:
         nt = _inflate_threads(kind)
-        gz = _lib.GzPool(paths, threads=nt, ahead=_lib.inflate_ahead(paths, nt))
+        reader = GpuReader(paths, nt, reader_chunk) if gz_reader == "gpu" else None
+        if reader is not None:
+            paths = reader.pool_paths
+        if reader is None or paths:
+            gz = _lib.GzPool(paths, threads=nt, ahead=_lib.inflate_ahead(paths, nt))
         st["setup: results, writers"] = clock() - t_start
         dmx = dev or _lib.Demux(device)
         pool = ThreadPoolExecutor(max_workers=max(2, min(32, n_dest * 2)))
@@ -1144,7 +1345,7 @@ def _session(t_start, paths, kind, n_dest, device, sheet, table, dev=None, ctx=N
         else:
             dmx.set_table(*table)
         st["setup"] = clock() - t_start  # results, writers, device table, pool
-        yield dmx, pool, gz
+        yield dmx, pool, gz, reader
     finally:
         t_end = clock()
         if gz is not None:
@@ -1180,6 +1381,7 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     cycles_file = cycle_stats_path(args)
     bstats_file = barcode_stats_path(args)
     fmt = gz_format(args)
+    gz_reader(args)  # refused here if it is neither host nor gpu, before anything is created
     single = single_index(args)
     num_subs = num_subs_of(*mismatch_limits(args)) if mode == "b" else None  # --n2 with --single-index: refused here
     samples = not args.no_samples
@@ -1238,7 +1440,8 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     paths = [str(f) for pr in pairs for f in pr]
     try:
         with _session(t_start, paths, kind, len(writers), _device_index(None), sheet, table, dev, ctx,
-                      lambda: _close_writers(writers, names, lazy, hit, args.d, infix)) as (dmx, pool, gz):
+                      lambda: _close_writers(writers, names, lazy, hit, args.d, infix), gz_reader(args),
+                      int(getattr(args, "gz_reader_chunk", 0) or 0)) as (dmx, pool, gz, reader):
             if report is not None:
                 report.begin(dmx)
             if stats is not None:
@@ -1255,8 +1458,10 @@ def frender_demux(args, dev=None, ctx=None) -> None:
                     if report is not None:
                         report.begin_pair(dmx, k)
                     _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers,
-                                window, sheet, hit, report, stats, cycles, bstats, validate)
+                                window, sheet, hit, report, stats, cycles, bstats, validate, reader)
             finally:
+                if reader is not None:
+                    READER_INFO.update({"R1": dmx.bgzf_info(0), "R2": dmx.bgzf_info(1)})
                 if validate is not None:  # a caller's dev goes back as it came: the validation off
                     validate.end(dmx)
             if sheet is not None and samples and not (hit & lazy):
@@ -1275,6 +1480,8 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     finally:
         STAGE_TIMES["total"] = time.perf_counter() - t_start
         if getattr(args, "stage_times", False):
+            if READER_INFO:
+                print(json.dumps({"reader": READER_INFO}), file=sys.stderr)
             print(json.dumps({k: round(v, 3) for k, v in STAGE_TIMES.items()}), file=sys.stderr)
 
 
@@ -1344,7 +1551,8 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
         # the session opens inside the try: a rank whose pool or device fails still joins the collectives below
         # (-b: this rank's own sheet context: classification is stateless, nothing is exchanged)
         with _session(t_start, [str(f) for k in mine for f in pairs[k]], kind, len(names), _device_index(group),
-                      sheet, table) as (dmx, pool, gz):
+                      sheet, table, gz_reader=gz_reader(args),
+                      reader_chunk=int(getattr(args, "gz_reader_chunk", 0) or 0)) as (dmx, pool, gz, reader):
             if report is not None:
                 report.begin(dmx)
             if stats is not None:
@@ -1364,7 +1572,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
                     if report is not None:
                         report.begin_pair(dmx, k)  # the global pair index: the ordinals are the one-process run's
                     _demux_pair(dmx, pool, gz, 2 * j, 2 * j + 1, pairs[k][0], pairs[k][1], results, route_of, writers,
-                                window, sheet, hit, report, stats, cycles, bstats, validate)
+                                window, sheet, hit, report, stats, cycles, bstats, validate, reader)
                 except (Exception, SystemExit) as e:  # re-raised below if it is the first in pair order
                     failed, exc = k, e
                 finally:

@@ -267,3 +267,11 @@ def gz_format(args) -> str:
         raise SystemExit(f"--gz-format bgzf needs --gz-writer gpu (got {writer}): the host writers make plain gzip "
                          "members only")
     return fmt
+
+
+def gz_reader(args) -> str:
+    """--gz-reader of a demux's arguments (a namespace without it means host): who inflates the BGZF inputs."""
+    r = getattr(args, "gz_reader", None) or "host"
+    if r not in ("host", "gpu"):
+        raise SystemExit(f"--gz-reader {r}: expected host or gpu")
+    return r

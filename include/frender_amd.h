@@ -564,6 +564,43 @@ int fr_dmx_validate_result(fr_dmx* d, int64_t* first_pair, int32_t* kind);
 /* Free the word and turn the validation off (fr_dmx_destroy does as much). */
 int fr_dmx_validate_end(fr_dmx* d);
 
+/* ---- `demux --gz-reader gpu` (fr_dmx_reader.hip): a mate's BGZF file is inflated on the GPU, window by window,
+ * into the buffer the window is indexed and routed from; its text reaches the host only through
+ * fr_dmx_window_read.  Nothing is allocated and nothing launched before the first fr_dmx_bgzf_open.
+ *
+ * fr_dmx_bgzf_open: *taken = 1 when the file's first member header is the one fr_bgzf_probe accepts (FLG ==
+ * FEXTRA alone, the BC subfield alone); the reader then holds the file and its staging: two pinned buffers of
+ * chunk_bytes (0: 32 MiB; at least one member) that a host thread fills ahead with whole members, and their
+ * device copy.  A file of any size is taken.  *taken = 0 with FR_OK: not such a file (or not readable: the host
+ * reader says why), nothing is held.  The members after the first are walked as the file streams; one that the
+ * probe would refuse hands the file over (below) where it stands.
+ *
+ * fr_dmx_bgzf_fill: the mate's next window.  keep_from: offset in the window at hand of the first byte to keep
+ * (0 on the first call: there is none).  The bytes from keep_from on (the carry) move to the front of the
+ * mate's other window buffer; whole members are decoded right behind them, each at carry + the decoded sizes
+ * before it, while the window holds fewer than `want` bytes and the file has members left (so it ends less
+ * than one member, 65536 bytes, past max(carry, want)); every member's status, CRC-32 and size are checked
+ * against its trailer and the new bytes must be 7-bit ASCII without '\r' (dmx_text_kernel); then the window is
+ * indexed as by fr_dmx_load_device: *n_records, *len.  *eof = 1: no member is left.  The call waits for the
+ * context's stream first, so whatever was queued on a window of this mate has read it.
+ * Hand-over: when a check fails (or the file cannot be read), *handed_over = 1, nothing of this call's
+ * members is delivered: the window is the carry alone (*len its length, no records), *resume is the decoded
+ * offset in the file of the first byte not delivered (every byte before it was ASCII without '\r'), and the
+ * file is closed: the host reader continues from there.  Otherwise *resume is the decoded offset after this
+ * window. */
+int fr_dmx_bgzf_open(fr_dmx* d, int mate, const char* path, uint64_t chunk_bytes, int* taken);
+int fr_dmx_bgzf_fill(fr_dmx* d, int mate, uint64_t keep_from, uint64_t want, uint64_t* n_records, uint64_t* len,
+                     int* eof, int* handed_over, uint64_t* resume);
+/* release the mate's file (the buffers stay for the next one); a mate without one: nothing */
+int fr_dmx_bgzf_close(fr_dmx* d, int mate);
+/* the mate's diagnostics since fr_dmx_create: out[0] files taken, [1] members decoded, [2] fills that delivered
+ * a window, [3] hand-overs, [4] the fill (0-based, in its file) at which the last hand-over happened (-1: none),
+ * [5] the last fill's inflate-kernel ms, [6] its text-kernel ms, [7] decoded bytes delivered */
+int fr_dmx_bgzf_info(fr_dmx* d, int mate, double out[8]);
+/* bytes [start, end) of the mate's window at hand, however it was loaded (fr_dmx_load*, fr_dmx_bgzf_fill): for
+ * the codes the host resolves, its messages and a hand-over's carry; one copy, whatever the span */
+int fr_dmx_window_read(fr_dmx* d, int mate, uint64_t start, uint64_t end, uint8_t* out);
+
 /* ---- GPU deflate over any byte ranges (fr_deflate.hip; fr_dmx_deflate runs it on the routed bytes).
  * Stream s is bytes [offsets[s], offsets[s + 1]) of the device buffer dev_data (4-byte aligned, 16
  * readable bytes past offsets[n_streams]); every stream becomes one raw deflate stream, no larger than
