@@ -134,6 +134,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="single-indexed library, as scan --single-index: with -r, a result row with an empty idx2 "
                         "also answers reads whose code has no '+'; with -b, reads are classified by index 1 alone "
                         "and the table needs no index-2 column")
+    d.add_argument("--single-end", action="store_true",
+                   help="single-read run: every fastq file given is demultiplexed on its own, by the barcode in its "
+                        "own header lines, into {name}_frender-demux_{infix_}R1.fq.gz files (no R2 files; the name "
+                        "needs no _R1_); goes with every other flag, the by-products cover read 1 alone and "
+                        "--validate checks the records of the one read; a read 1 / read 2 pair among the files is "
+                        "refused (-r and -b; with --gpus, files are dealt to the GPUs)")
     d.add_argument("--stage-times", action="store_true", help="print the demux's seconds per stage (stderr)")
     d.add_argument("files", nargs="+", help="Fastq file, list of fastq files, or directory path")
     d.set_defaults(cmd="demux")

@@ -154,6 +154,7 @@ _SIGS = {
     "fr_dmx_set_table": (C.c_int, [P, P, P, C.c_uint64]),
     "fr_dmx_set_sheet": (C.c_int, [P, P, C.c_int, P, C.c_int, P]),
     "fr_dmx_set_sheet2": (C.c_int, [P, P, C.c_int, C.c_int, P, C.c_int, P]),
+    "fr_dmx_set_mates": (C.c_int, [P, C.c_int]),
     "fr_dmx_load": (C.c_int, [P, C.c_int, P, C.c_uint64, u64p]),
     "fr_dmx_load_device": (C.c_int, [P, C.c_int, P, C.c_uint64, u64p]),
     "fr_dmx_records": (C.c_int, [P, C.c_int, P, C.c_uint64, P, P]),
@@ -539,6 +540,10 @@ class Demux:
         else:
             self._ck(lib.fr_dmx_set_sheet2(self.h, ctx.h, n1, n2, _ptr(rd), rd.size, _ptr(cd)), "fr_dmx_set_sheet2")
         self._sheet_ctx = ctx
+
+    def set_mates(self, n_mates: int):
+        """fr_dmx_set_mates: 1 for single-end inputs (mate 0 is the only mate, and the code mate), 2 for pairs."""
+        self._ck(lib.fr_dmx_set_mates(self.h, int(n_mates)), "fr_dmx_set_mates")
 
     def load(self, mate: int, data) -> int:
         a = np.frombuffer(data, dtype=np.uint8)

@@ -315,6 +315,14 @@ __global__ void dmx_lengths(const u32* perm, u64 n, const u64* rs1, const u64* r
     }
 }
 
+// the same for the only mate there is (fr_dmx_set_mates(1))
+__global__ void dmx_lengths1(const u32* perm, u64 n, const u64* rs, u64* len) {
+    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x) {
+        const u32 i = perm[j];
+        len[j] = rs[i + 1] - rs[i];
+    }
+}
+
 // first partition position of every destination present (sorted keys: one boundary each, no atomics)
 __global__ void dmx_bounds(const u32* sk, u64 n, u32* first) {
     for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x)
@@ -332,6 +340,15 @@ __global__ void dmx_dest_offsets(const u32* first, int n_dest, u64 n, const u64*
     while (e < n_dest && first[e] == 0xFFFFFFFFu) ++e;
     off1[d] = e < n_dest ? o1[first[e]] : tot1;
     off2[d] = e < n_dest ? o2[first[e]] : tot2;
+}
+
+// the same for the only mate there is (fr_dmx_set_mates(1))
+__global__ void dmx_dest_offsets1(const u32* first, int n_dest, u64 n, const u64* o, const u64* l, u64* off) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d > n_dest) return;
+    int e = d;
+    while (e < n_dest && first[e] == 0xFFFFFFFFu) ++e;
+    off[d] = e < n_dest ? o[first[e]] : o[n - 1] + l[n - 1];
 }
 
 // one wave per output record: a byte head up to the destination's 4-byte alignment, then
@@ -375,6 +392,9 @@ struct fr_dmx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
+    // the mates of an input (fr_dmx_set_mates): 2, or 1 for a single-end file, whose only mate (0) is the code mate
+    int n_mates = 2;
+    int code_mate() const { return n_mates - 1; }
     // results table
     u64* tkeys = nullptr;
     int32_t* tvals = nullptr;
@@ -462,6 +482,13 @@ static hipError_t ensure(T** p, u64& cap, u64 n) {
     }
     cap = std::max<u64>(n + n / 4, 1024);
     return hipMalloc((void**)p, cap * sizeof(T));
+}
+
+// one-mate mode (fr_dmx_set_mates(1)) has no mate 1: the entry point `what` refuses it
+static bool no_mate(fr_dmx* d, int mate, const char* what) {
+    if (d->n_mates == 2 || mate != 1) return false;
+    d->err = std::string(what) + ": there is no mate 1 in one-mate mode (fr_dmx_set_mates(1))";
+    return true;
 }
 
 extern "C" {
@@ -559,12 +586,30 @@ int fr_dmx_set_sheet2(fr_dmx* d, fr_ctx* ctx, int num_subs1, int num_subs2, cons
     return FR_OK;
 }
 
+int fr_dmx_set_mates(fr_dmx* d, int n_mates) {
+    if (n_mates != 1 && n_mates != 2) return d->err = "fr_dmx_set_mates: n_mates must be 1 or 2", FR_ERR_INVALID;
+    if (n_mates == d->n_mates) return FR_OK;
+    if (d->len[0] || d->len[1] || dmx_reader_is_open(d->reader, 0) || dmx_reader_is_open(d->reader, 1))
+        return d->err = "fr_dmx_set_mates: a mate is loaded or a BGZF mate is open (the count changes between inputs, "
+                        "with no window at hand)", FR_ERR_INVALID;
+    DK(hipSetDevice(d->device));
+    DK(hipStreamSynchronize(d->stream));
+    d->n_mates = n_mates;
+    d->nrec[0] = d->nrec[1] = 0;
+    d->out_len[0] = d->out_len[1] = 0;
+    d->routed_ok = d->stats_ok = d->cycles_ok = d->bstats_ok = 0;
+    d->vloaded[0] = d->vloaded[1] = false;
+    d->rbin_loaded = false;
+    return FR_OK;
+}
+
 static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_records) {
+    const bool code = mate == d->code_mate();  // the mate whose header carries the record's code
     d->src[mate] = buf;
     d->len[mate] = len;
     d->routed_ok = d->stats_ok = d->cycles_ok = d->bstats_ok = 0;
     d->vloaded[mate] = false;
-    if (mate == 1) d->rbin_loaded = false;
+    if (code) d->rbin_loaded = false;
     const u32 ntiles = (u32)((len + DT - 1) / DT);
     DK(ensure(&d->cnt, d->c_cnt, (u64)ntiles + 1));
     DK(ensure(&d->base, d->c_base, (u64)ntiles + 1));
@@ -588,11 +633,11 @@ static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_re
     const u64 lines = nl + ((len && lastb != '\n') ? 1 : 0);  // a last line without '\n'
     const u64 nrec = (lines + 3) / 4;
     DK(ensure(&d->rs[mate], d->rs_cap[mate], nrec + 1));
-    if (mate == 1) DK(ensure(&d->dest, d->dest_cap, nrec + 1));
+    if (code) DK(ensure(&d->dest, d->dest_cap, nrec + 1));
     d->nrec[mate] = nrec;
     *n_records = nrec;
     DK(hipMemcpyAsync(d->rs[mate] + nrec, &d->len[mate], 8, hipMemcpyHostToDevice, d->stream));  // sentinel
-    if (ntiles && mate == 1 && d->key_mode) {
+    if (ntiles && code && d->key_mode) {
         DK(ensure(&d->rkey, d->rkey_cap, nrec + 1));
         hipLaunchKernelGGL(dmx_index<true>, dim3(std::min<u32>(ntiles, 4096)), dim3(DWG), 0, d->stream, buf, len,
                            ntiles, d->base, d->rs[mate], d->dest, DmxTable{nullptr, nullptr, 0}, d->rkey);
@@ -604,7 +649,7 @@ static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_re
     } else if (ntiles) {
         DmxTable tab{d->tkeys, d->tvals, d->tmask};
         hipLaunchKernelGGL(dmx_index<false>, dim3(std::min<u32>(ntiles, 4096)), dim3(DWG), 0, d->stream, buf, len,
-                           ntiles, d->base, d->rs[mate], mate == 1 ? d->dest : nullptr, tab, (u64*)nullptr);
+                           ntiles, d->base, d->rs[mate], code ? d->dest : nullptr, tab, (u64*)nullptr);
         DK(hipGetLastError());
     }
     DK(hipStreamSynchronize(d->stream));
@@ -614,6 +659,7 @@ static int dmx_index_mate(fr_dmx* d, int mate, const u8* buf, u64 len, u64* n_re
 
 int fr_dmx_load(fr_dmx* d, int mate, const uint8_t* data, uint64_t len, uint64_t* n_records) {
     if (mate < 0 || mate > 1) return d->err = "mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    if (no_mate(d, mate, "fr_dmx_load")) return FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     DK(ensure(&d->data[mate], d->cap[mate], len + 16));
     if (len) DK(hipMemcpyAsync(d->data[mate], data, len, hipMemcpyHostToDevice, d->stream));
@@ -623,6 +669,7 @@ int fr_dmx_load(fr_dmx* d, int mate, const uint8_t* data, uint64_t len, uint64_t
 int fr_dmx_load_parts(fr_dmx* d, int mate, const uint8_t* const* parts, const uint64_t* lens, int n_parts,
                       uint64_t* n_records) {
     if (mate < 0 || mate > 1 || n_parts < 0) return d->err = "mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    if (no_mate(d, mate, "fr_dmx_load_parts")) return FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     u64 len = 0;
     for (int k = 0; k < n_parts; ++k) len += lens[k];
@@ -637,12 +684,14 @@ int fr_dmx_load_parts(fr_dmx* d, int mate, const uint8_t* const* parts, const ui
 
 int fr_dmx_load_device(fr_dmx* d, int mate, const uint8_t* dev_data, uint64_t len, uint64_t* n_records) {
     if (mate < 0 || mate > 1) return d->err = "mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    if (no_mate(d, mate, "fr_dmx_load_device")) return FR_ERR_INVALID;
     if (((uintptr_t)dev_data & 15u) != 0) return d->err = "device data must be 16-byte aligned", FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     return dmx_index_mate(d, mate, dev_data, len, n_records);
 }
 
 int fr_dmx_records(fr_dmx* d, int mate, const uint64_t* recs, uint64_t n, uint64_t* starts, uint64_t* ends) {
+    if (no_mate(d, mate, "fr_dmx_records")) return FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     std::vector<u64> all;
     for (u64 k = 0; k < n; ++k)
@@ -667,7 +716,7 @@ int fr_dmx_records(fr_dmx* d, int mate, const uint64_t* recs, uint64_t n, uint64
 
 int fr_dmx_exotic(fr_dmx* d, uint64_t n_pairs, uint64_t* recs, uint64_t cap, uint64_t* n) {
     DK(hipSetDevice(d->device));
-    n_pairs = std::min<u64>(n_pairs, d->nrec[1]);
+    n_pairs = std::min<u64>(n_pairs, d->nrec[d->code_mate()]);
     std::vector<int32_t> h(n_pairs);
     if (n_pairs) DK(hipMemcpy(h.data(), d->dest, n_pairs * 4, hipMemcpyDeviceToHost));
     u64 k = 0;
@@ -683,9 +732,9 @@ int fr_dmx_exotic(fr_dmx* d, uint64_t n_pairs, uint64_t* recs, uint64_t cap, uin
 int fr_dmx_patch(fr_dmx* d, const uint64_t* recs, const int32_t* dest, uint64_t n) {
     DK(hipSetDevice(d->device));
     for (u64 k = 0; k < n; ++k)
-        if (recs[k] >= d->nrec[1]) return d->err = "record index out of range", FR_ERR_INVALID;
+        if (recs[k] >= d->nrec[d->code_mate()]) return d->err = "record index out of range", FR_ERR_INVALID;
     if (n >= DMX_BATCH) {  // many records: the whole array there and back, two copies
-        std::vector<int32_t> all(d->nrec[1]);
+        std::vector<int32_t> all(d->nrec[d->code_mate()]);
         DK(hipMemcpy(all.data(), d->dest, all.size() * 4, hipMemcpyDeviceToHost));
         for (u64 k = 0; k < n; ++k) all[recs[k]] = dest[k];
         DK(hipMemcpy(d->dest, all.data(), all.size() * 4, hipMemcpyHostToDevice));
@@ -700,8 +749,10 @@ int fr_dmx_patch(fr_dmx* d, const uint64_t* recs, const int32_t* dest, uint64_t 
 int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, int32_t* error_val,
                  uint64_t* bytes_r1, uint64_t* bytes_r2) {
     DK(hipSetDevice(d->device));
-    const u64 P = std::min<u64>({n_pairs, d->nrec[0], d->nrec[1]});
-    if (P >= 0xFFFFFFFFull) return d->err = "too many records in one file pair", FR_ERR_CAPACITY;
+    const bool paired = d->n_mates == 2;
+    const u64 P = std::min<u64>({n_pairs, d->nrec[0], d->nrec[d->code_mate()]});
+    if (P >= 0xFFFFFFFFull)
+        return d->err = paired ? "too many records in one file pair" : "too many records in one file", FR_ERR_CAPACITY;
     *first_error = -1;
     *error_val = 0;
     d->routed_ok = d->stats_ok = d->cycles_ok = d->bstats_ok = 0;
@@ -734,12 +785,14 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     DK(ensure(&d->i_in, d->c_i_in, P));
     DK(ensure(&d->perm, d->c_perm, P));
     DK(ensure(&d->l1, d->c_l1, P));
-    DK(ensure(&d->l2, d->c_l2, P));
     DK(ensure(&d->o1, d->c_o1, P));
-    DK(ensure(&d->o2, d->c_o2, P));
     DK(ensure(&d->first_pos, d->c_first, (u64)std::max(n_dest, 1)));
     DK(ensure(&d->off1, d->c_off1, (u64)n_dest + 1));
-    DK(ensure(&d->off2, d->c_off2, (u64)n_dest + 1));
+    if (paired) {  // (one mate: nothing of mate 1's is allocated, scanned, copied or read back)
+        DK(ensure(&d->l2, d->c_l2, P));
+        DK(ensure(&d->o2, d->c_o2, P));
+        DK(ensure(&d->off2, d->c_off2, (u64)n_dest + 1));
+    }
     u32 *k_in = d->k_in, *k_out = d->k_out, *i_in = d->i_in, *perm = d->perm, *first_pos = d->first_pos;
     u64 *l1 = d->l1, *l2 = d->l2, *o1 = d->o1, *o2 = d->o2, *off1 = d->off1, *off2 = d->off2;
     DK(hipMemsetAsync(first_pos, 0xFF, (u64)std::max(n_dest, 1) * 4, d->stream));
@@ -754,18 +807,26 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     DK(ensure((u8**)&d->tmp, d->c_tmp, std::max<size_t>(std::max(tb, tb2), 1)));
     void* tmp = d->tmp;
     DK(rocprim::radix_sort_pairs(tmp, tb, k_in, k_out, i_in, perm, (size_t)P, 0, (unsigned)bits, d->stream));
-    hipLaunchKernelGGL(dmx_lengths, dim3(grid_for(P)), dim3(256), 0, d->stream, perm, P, d->rs[0], d->rs[1], l1, l2);
+    if (paired)
+        hipLaunchKernelGGL(dmx_lengths, dim3(grid_for(P)), dim3(256), 0, d->stream, perm, P, d->rs[0], d->rs[1], l1, l2);
+    else
+        hipLaunchKernelGGL(dmx_lengths1, dim3(grid_for(P)), dim3(256), 0, d->stream, perm, P, d->rs[0], l1);
     DK(hipGetLastError());
     hipLaunchKernelGGL(dmx_bounds, dim3(grid_for(P)), dim3(256), 0, d->stream, k_out, P, first_pos);
     DK(hipGetLastError());
     DK(rocprim::exclusive_scan(tmp, tb2, l1, o1, (u64)0, (size_t)P, rocprim::plus<u64>(), d->stream));
-    DK(rocprim::exclusive_scan(tmp, tb2, l2, o2, (u64)0, (size_t)P, rocprim::plus<u64>(), d->stream));
-    hipLaunchKernelGGL(dmx_dest_offsets, dim3((n_dest + 256) / 256), dim3(256), 0, d->stream, first_pos, n_dest, P,
-                       o1, l1, o2, l2, off1, off2);
+    if (paired) {
+        DK(rocprim::exclusive_scan(tmp, tb2, l2, o2, (u64)0, (size_t)P, rocprim::plus<u64>(), d->stream));
+        hipLaunchKernelGGL(dmx_dest_offsets, dim3((n_dest + 256) / 256), dim3(256), 0, d->stream, first_pos, n_dest, P,
+                           o1, l1, o2, l2, off1, off2);
+    } else {
+        hipLaunchKernelGGL(dmx_dest_offsets1, dim3((n_dest + 256) / 256), dim3(256), 0, d->stream, first_pos, n_dest, P,
+                           o1, l1, off1);
+    }
     DK(hipGetLastError());
-    std::vector<u64> h1(n_dest + 1), h2(n_dest + 1);
+    std::vector<u64> h1(n_dest + 1), h2(n_dest + 1, 0);
     DK(hipMemcpyAsync(h1.data(), off1, (n_dest + 1) * 8, hipMemcpyDeviceToHost, d->stream));
-    DK(hipMemcpyAsync(h2.data(), off2, (n_dest + 1) * 8, hipMemcpyDeviceToHost, d->stream));
+    if (paired) DK(hipMemcpyAsync(h2.data(), off2, (n_dest + 1) * 8, hipMemcpyDeviceToHost, d->stream));
     DK(hipStreamSynchronize(d->stream));
     for (int k = 0; k < n_dest; ++k) {
         bytes_r1[k] = h1[k + 1] - h1[k];
@@ -773,12 +834,14 @@ int fr_dmx_route(fr_dmx* d, int n_dest, uint64_t n_pairs, int64_t* first_error, 
     }
     const u64 s1 = h1[n_dest], s2 = h2[n_dest];
     DK(ensure(&d->out[0], d->out_cap[0], s1 + 16));
-    DK(ensure(&d->out[1], d->out_cap[1], s2 + 16));
+    if (paired) DK(ensure(&d->out[1], d->out_cap[1], s2 + 16));
     const int cg = grid_for(P, 4, 16384);
     hipLaunchKernelGGL(dmx_copy, dim3(cg), dim3(256), 0, d->stream, perm, P, d->rs[0], d->src[0], o1, d->out[0]);
     DK(hipGetLastError());
-    hipLaunchKernelGGL(dmx_copy, dim3(cg), dim3(256), 0, d->stream, perm, P, d->rs[1], d->src[1], o2, d->out[1]);
-    DK(hipGetLastError());
+    if (paired) {
+        hipLaunchKernelGGL(dmx_copy, dim3(cg), dim3(256), 0, d->stream, perm, P, d->rs[1], d->src[1], o2, d->out[1]);
+        DK(hipGetLastError());
+    }
     DK(hipStreamSynchronize(d->stream));
     d->out_len[0] = s1;
     d->out_len[1] = s2;
@@ -856,6 +919,8 @@ int fr_dmx_stats_window(fr_dmx* d, uint64_t n_pairs) {
                FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     d->stats_ok = 0;
+    if (d->n_mates == 1)  // the launch covers mate 0 alone: mate 1's half of the accumulators stays zero
+        return dmx_stats_window(d->stats, d->out[0], nullptr, d->o1, d->l1, nullptr, nullptr, d->k_out, n_pairs, d->err);
     return dmx_stats_window(d->stats, d->out[0], d->out[1], d->o1, d->l1, d->o2, d->l2, d->k_out, n_pairs, d->err);
 }
 
@@ -887,6 +952,9 @@ int fr_dmx_cycles_window(fr_dmx* d, uint64_t n_pairs) {
                FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     d->cycles_ok = 0;
+    if (d->n_mates == 1)  // as fr_dmx_stats_window
+        return dmx_cycles_window(d->cycles, d->out[0], nullptr, d->o1, d->l1, nullptr, nullptr, d->k_out, n_pairs,
+                                 d->err);
     return dmx_cycles_window(d->cycles, d->out[0], d->out[1], d->o1, d->l1, d->o2, d->l2, d->k_out, n_pairs, d->err);
 }
 
@@ -908,12 +976,14 @@ int fr_dmx_bstats_begin(fr_dmx* d, int n_dest) {
 
 int fr_dmx_bstats_patch(fr_dmx* d, const uint64_t* recs, const uint8_t* bins, uint64_t n) {
     if (!d->bstats || !d->rbin_loaded)
-        return d->err = "fr_dmx_bstats_patch: no R2 window loaded since fr_dmx_bstats_begin", FR_ERR_INVALID;
+        return d->err = d->n_mates == 2 ? "fr_dmx_bstats_patch: no R2 window loaded since fr_dmx_bstats_begin"
+                                        : "fr_dmx_bstats_patch: no window loaded since fr_dmx_bstats_begin",
+               FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     for (u64 k = 0; k < n; ++k)
-        if (recs[k] >= d->nrec[1]) return d->err = "record index out of range", FR_ERR_INVALID;
+        if (recs[k] >= d->nrec[d->code_mate()]) return d->err = "record index out of range", FR_ERR_INVALID;
     if (n >= DMX_BATCH) {  // many records: the whole array there and back, two copies
-        std::vector<u8> all(d->nrec[1]);
+        std::vector<u8> all(d->nrec[d->code_mate()]);
         DK(hipMemcpy(all.data(), d->rbin, all.size(), hipMemcpyDeviceToHost));
         for (u64 k = 0; k < n; ++k) all[recs[k]] = bins[k];
         DK(hipMemcpy(d->rbin, all.data(), all.size(), hipMemcpyHostToDevice));
@@ -955,13 +1025,18 @@ int fr_dmx_validate_begin(fr_dmx* d) {
 
 int fr_dmx_validate_window(fr_dmx* d, uint64_t n_pairs) {
     if (!d->validate) return d->err = "fr_dmx_validate_window: no fr_dmx_validate_begin", FR_ERR_INVALID;
-    if (!d->vloaded[0] || !d->vloaded[1])
-        return d->err = "fr_dmx_validate_window: not both mates are loaded since the last fr_dmx_validate_window",
+    const int cm = d->code_mate();
+    if (!d->vloaded[0] || !d->vloaded[cm])
+        return d->err = cm ? "fr_dmx_validate_window: not both mates are loaded since the last fr_dmx_validate_window"
+                           : "fr_dmx_validate_window: the mate is not loaded since the last fr_dmx_validate_window",
                FR_ERR_INVALID;
-    if (n_pairs > std::min(d->nrec[0], d->nrec[1]))
-        return d->err = "fr_dmx_validate_window: n_pairs is beyond a mate's records", FR_ERR_INVALID;
+    if (n_pairs > std::min(d->nrec[0], d->nrec[cm]))
+        return d->err = cm ? "fr_dmx_validate_window: n_pairs is beyond a mate's records"
+                           : "fr_dmx_validate_window: n_pairs is beyond the mate's records", FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
-    const int rc = dmx_validate_window(d->validate, d->src[0], d->src[1], d->rs[0], d->rs[1], n_pairs, d->err);
+    // one mate: no second buffer, the kernel's instantiation that checks kinds 1-4 of mate 0 alone
+    const int rc = cm ? dmx_validate_window(d->validate, d->src[0], d->src[1], d->rs[0], d->rs[1], n_pairs, d->err)
+                      : dmx_validate_window(d->validate, d->src[0], nullptr, d->rs[0], nullptr, n_pairs, d->err);
     if (rc == FR_OK) {
         d->vloaded[0] = d->vloaded[1] = false;
         d->vqueued = true;
@@ -988,11 +1063,13 @@ int fr_dmx_validate_end(fr_dmx* d) {
 // files, the staging and the window buffers are fr_dmx_reader.hip's
 int fr_dmx_bgzf_open(fr_dmx* d, int mate, const char* path, uint64_t chunk_bytes, int* taken) {
     if (mate < 0 || mate > 1 || !taken) return d->err = "fr_dmx_bgzf_open: mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    if (no_mate(d, mate, "fr_dmx_bgzf_open")) return FR_ERR_INVALID;
     return dmx_reader_open(&d->reader, d->device, d->stream, mate, path, chunk_bytes, taken, d->err);
 }
 
 int fr_dmx_bgzf_fill(fr_dmx* d, int mate, uint64_t keep_from, uint64_t want, uint64_t* n_records, uint64_t* len,
                      int* eof, int* handed_over, uint64_t* resume) {
+    if (no_mate(d, mate, "fr_dmx_bgzf_fill")) return FR_ERR_INVALID;
     if (mate < 0 || mate > 1 || !dmx_reader_is_open(d->reader, mate))
         return d->err = "fr_dmx_bgzf_fill: no file is open for the mate (fr_dmx_bgzf_open)", FR_ERR_INVALID;
     const u8* win = nullptr;
@@ -1005,7 +1082,7 @@ int fr_dmx_bgzf_fill(fr_dmx* d, int mate, uint64_t keep_from, uint64_t want, uin
         d->nrec[mate] = 0;
         d->routed_ok = d->stats_ok = d->cycles_ok = d->bstats_ok = 0;
         d->vloaded[mate] = false;
-        if (mate == 1) d->rbin_loaded = false;
+        if (mate == d->code_mate()) d->rbin_loaded = false;
         return FR_OK;
     }
     return dmx_index_mate(d, mate, win, *len, n_records);
@@ -1013,18 +1090,21 @@ int fr_dmx_bgzf_fill(fr_dmx* d, int mate, uint64_t keep_from, uint64_t want, uin
 
 int fr_dmx_bgzf_close(fr_dmx* d, int mate) {
     if (mate < 0 || mate > 1) return d->err = "fr_dmx_bgzf_close: mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    if (no_mate(d, mate, "fr_dmx_bgzf_close")) return FR_ERR_INVALID;
     dmx_reader_close(d->reader, mate);
     return FR_OK;
 }
 
 int fr_dmx_bgzf_info(fr_dmx* d, int mate, double out[8]) {
     if (mate < 0 || mate > 1 || !out) return d->err = "fr_dmx_bgzf_info: mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    if (no_mate(d, mate, "fr_dmx_bgzf_info")) return FR_ERR_INVALID;
     dmx_reader_info(d->reader, mate, out);
     return FR_OK;
 }
 
 int fr_dmx_window_read(fr_dmx* d, int mate, uint64_t start, uint64_t end, uint8_t* out) {
     if (mate < 0 || mate > 1) return d->err = "fr_dmx_window_read: mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    if (no_mate(d, mate, "fr_dmx_window_read")) return FR_ERR_INVALID;
     if (start > end || end > d->len[mate] || (end > start && !d->src[mate]))
         return d->err = "fr_dmx_window_read: the span is not inside the mate's window", FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
@@ -1035,6 +1115,7 @@ int fr_dmx_window_read(fr_dmx* d, int mate, uint64_t start, uint64_t end, uint8_
 // the routed bytes of a mate through its fr_defl: gzip streams (crc32 set) or BGZF member runs
 static int dmx_deflate(fr_dmx* d, int mate, int n_dest, uint64_t* comp_bytes, uint32_t* crc32, bool bgzf) {
     if (mate < 0 || mate > 1) return d->err = "mate must be 0 (R1) or 1 (R2)", FR_ERR_INVALID;
+    if (no_mate(d, mate, "fr_dmx_deflate")) return FR_ERR_INVALID;
     if (n_dest < 0 || (u64)n_dest + 1 != d->hoff[mate].size())
         return d->err = "fr_dmx_deflate: n_dest differs from the last fr_dmx_route", FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
@@ -1058,6 +1139,7 @@ int fr_dmx_deflate_bgzf(fr_dmx* d, int mate, int n_dest, uint64_t* comp_bytes) {
 }
 
 int fr_dmx_fetch_deflated(fr_dmx* d, int mate, uint8_t* out, uint64_t len) {
+    if (no_mate(d, mate, "fr_dmx_fetch_deflated")) return FR_ERR_INVALID;
     if (mate < 0 || mate > 1 || !d->defl[mate]) return d->err = "fr_dmx_fetch_deflated: bad mate or no fr_dmx_deflate", FR_ERR_INVALID;
     const int rc = fr_defl_fetch(d->defl[mate], out, len);
     if (rc != FR_OK) d->err = std::string("fr_dmx_fetch_deflated: ") + fr_defl_last_error(d->defl[mate]);
@@ -1065,6 +1147,7 @@ int fr_dmx_fetch_deflated(fr_dmx* d, int mate, uint8_t* out, uint64_t len) {
 }
 
 int fr_dmx_fetch(fr_dmx* d, int mate, uint8_t* out, uint64_t len) {
+    if (no_mate(d, mate, "fr_dmx_fetch")) return FR_ERR_INVALID;
     if (mate < 0 || mate > 1 || len > d->out_len[mate]) return d->err = "fr_dmx_fetch: bad mate or length", FR_ERR_INVALID;
     DK(hipSetDevice(d->device));
     if (len) DK(hipMemcpy(out, d->out[mate], len, hipMemcpyDeviceToHost));

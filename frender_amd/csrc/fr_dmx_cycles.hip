@@ -99,8 +99,8 @@ __device__ __forceinline__ void add_lines(const u8* buf, u64 sa, u64 sb, u64 qa,
     }
 }
 
-// grid (workgroups, 2 mates); workgroup g of a mate takes partition positions [g * per_wg, (g + 1) * per_wg);
-// dynamic LDS: u32 [CF][mc]
+// grid (workgroups, mates); workgroup g of a mate takes partition positions [g * per_wg, (g + 1) * per_wg); mates is 2,
+// or 1 for a single-end window, whose out2 / o2 / l2 are null and never read; dynamic LDS: u32 [CF][mc]
 __global__ __launch_bounds__(CWG) void dmx_cycles_kernel(const u8* out1, const u8* out2, const u64* o1, const u64* l1,
                                                          const u64* o2, const u64* l2, const u32* __restrict__ dest,
                                                          u64 n, u32 per_wg, int n_dest, u32 mc, u64* acc) {
@@ -272,8 +272,8 @@ int dmx_cycles_window(DmxCycles* t, const u8* out1, const u8* out2, const u64* o
     gx = std::max(gx, (n + CMAXRANGE - 1) / CMAXRANGE);  // n < 2^32 (fr_dmx_route's bound): at most 4096
     const u64 per_wg = (n + gx - 1) / gx;                // <= CMAXRANGE: the bound on a 32-bit bin
     const size_t lds = (size_t)CF * (size_t)t->max_cycles * sizeof(u32);
-    hipLaunchKernelGGL(dmx_cycles_kernel, dim3((unsigned)gx, 2), dim3(CWG), lds, t->stream, out1, out2, o1, l1, o2, l2,
-                       dest, n, (u32)per_wg, t->n_dest, (u32)t->max_cycles, t->acc);
+    hipLaunchKernelGGL(dmx_cycles_kernel, dim3((unsigned)gx, out2 ? 2 : 1), dim3(CWG), lds, t->stream, out1, out2, o1, l1,
+                       o2, l2, dest, n, (u32)per_wg, t->n_dest, (u32)t->max_cycles, t->acc);
     CK(hipGetLastError());
     return FR_OK;
 }

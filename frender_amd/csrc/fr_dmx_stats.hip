@@ -111,7 +111,8 @@ __device__ __forceinline__ void add_record(const u8* buf, u64 o, u64 L, const ui
     }
 }
 
-// grid (workgroups, 2 mates); wave w of a mate takes partition positions [w * per_wave, (w + 1) * per_wave)
+// grid (workgroups, mates); wave w of a mate takes partition positions [w * per_wave, (w + 1) * per_wave).  mates is
+// 2, or 1 for a single-end window, whose out2 / o2 / l2 are null and never read
 __global__ __launch_bounds__(SWG) void dmx_stats_kernel(const u8* out1, const u8* out2, const u64* o1, const u64* l1,
                                                         const u64* o2, const u64* l2, const u32* __restrict__ dest,
                                                         u64 n, u32 per_wave, int n_dest, u64* acc) {
@@ -236,8 +237,8 @@ int dmx_stats_window(DmxStats* t, const u8* out1, const u8* out2, const u64* o1,
     if (!n) return FR_OK;
     const u64 gx = std::max<u64>(1, std::min<u64>((n + SWAVES * SPER - 1) / (SWAVES * SPER), (u64)SGRID));
     const u64 per_wave = (n + gx * SWAVES - 1) / (gx * SWAVES);  // n < 2^32: fr_dmx_route's bound
-    hipLaunchKernelGGL(dmx_stats_kernel, dim3((unsigned)gx, 2), dim3(SWG), 0, t->stream, out1, out2, o1, l1, o2, l2,
-                       dest, n, (u32)per_wave, t->n_dest, t->acc);
+    hipLaunchKernelGGL(dmx_stats_kernel, dim3((unsigned)gx, out2 ? 2 : 1), dim3(SWG), 0, t->stream, out1, out2, o1, l1,
+                       o2, l2, dest, n, (u32)per_wave, t->n_dest, t->acc);
     SK(hipGetLastError());
     return FR_OK;
 }

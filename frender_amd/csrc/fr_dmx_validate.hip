@@ -123,7 +123,10 @@ __device__ __forceinline__ u64 strip_mate(const u8* buf, const Rec& r, u64 s, u6
     return c == (u32)'1' || c == (u32)'2' ? t - 2 : t;
 }
 
-// grid-strided, one wave per pair: pair k is record k of rs1 (bytes of b1) with record k of rs2 (bytes of b2)
+// grid-strided, one wave per pair: pair k is record k of rs1 (bytes of b1) with record k of rs2 (bytes of b2).
+// PAIRED = false (a single-end window, fr_dmx_set_mates(1)): record k of rs1 alone, kinds 1-4; b2 and rs2 are null
+// and never read
+template <bool PAIRED>
 __global__ __launch_bounds__(VWG) void dmx_validate_kernel(const u8* __restrict__ b1, const u8* __restrict__ b2,
                                                            const u64* __restrict__ rs1, const u64* __restrict__ rs2,
                                                            u64 n, unsigned long long* res) {
@@ -131,25 +134,31 @@ __global__ __launch_bounds__(VWG) void dmx_validate_kernel(const u8* __restrict_
     const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const u64 nw = (u64)gridDim.x * VWAVES;
     for (u64 k = (u64)blockIdx.x * VWAVES + (u64)wid; k < n; k += nw) {
-        Rec A, B;
+        Rec A;
         parse(b1, rs1[k], rs1[k + 1], lane, A);
-        parse(b2, rs2[k], rs2[k + 1], lane, B);
-        u32 kind = record_kind(b1, A);
-        if (!kind) {
-            kind = record_kind(b2, B);
-            if (kind) kind += 4;
-        }
-        if (!kind) {
-            u64 t1, c1, t2, c2;
-            scan_header(b1, A, lane, t1, c1);
-            scan_header(b2, B, lane, t2, c2);
-            const u64 s1 = A.o + 1, s2 = B.o + 1;  // after the '@'
-            t1 = strip_mate(b1, A, s1, t1);
-            t2 = strip_mate(b2, B, s2, t2);
-            if (t1 - s1 != t2 - s2 || !same_bytes(b1, s1, b2, s2, t1 - s1, lane))
-                kind = FR_DMX_V_NAME;
-            else if (A.n0 - c1 != B.n0 - c2 || !same_bytes(b1, c1, b2, c2, A.n0 - c1, lane))
-                kind = FR_DMX_V_CODE;
+        u32 kind;
+        if constexpr (PAIRED) {
+            Rec B;
+            parse(b2, rs2[k], rs2[k + 1], lane, B);
+            kind = record_kind(b1, A);
+            if (!kind) {
+                kind = record_kind(b2, B);
+                if (kind) kind += 4;
+            }
+            if (!kind) {
+                u64 t1, c1, t2, c2;
+                scan_header(b1, A, lane, t1, c1);
+                scan_header(b2, B, lane, t2, c2);
+                const u64 s1 = A.o + 1, s2 = B.o + 1;  // after the '@'
+                t1 = strip_mate(b1, A, s1, t1);
+                t2 = strip_mate(b2, B, s2, t2);
+                if (t1 - s1 != t2 - s2 || !same_bytes(b1, s1, b2, s2, t1 - s1, lane))
+                    kind = FR_DMX_V_NAME;
+                else if (A.n0 - c1 != B.n0 - c2 || !same_bytes(b1, c1, b2, c2, A.n0 - c1, lane))
+                    kind = FR_DMX_V_CODE;
+            }
+        } else {
+            kind = record_kind(b1, A);
         }
         if (kind && lane == 0) atomicMin(res, (unsigned long long)((k << 8) | kind));
     }
@@ -194,7 +203,12 @@ int dmx_validate_window(DmxValidate* t, const u8* b1, const u8* b2, const u64* r
     VK(hipMemsetAsync(t->word, 0xFF, sizeof(unsigned long long), t->stream));
     if (!n) return FR_OK;
     const u64 gx = std::min<u64>((n + VWAVES - 1) / VWAVES, (u64)VGRID);
-    hipLaunchKernelGGL(dmx_validate_kernel, dim3((unsigned)gx), dim3(VWG), 0, t->stream, b1, b2, rs1, rs2, n, t->word);
+    if (b2)
+        hipLaunchKernelGGL(dmx_validate_kernel<true>, dim3((unsigned)gx), dim3(VWG), 0, t->stream, b1, b2, rs1, rs2, n,
+                           t->word);
+    else
+        hipLaunchKernelGGL(dmx_validate_kernel<false>, dim3((unsigned)gx), dim3(VWG), 0, t->stream, b1, b2, rs1, rs2, n,
+                           t->word);
     VK(hipGetLastError());
     return FR_OK;
 }

@@ -24,6 +24,10 @@ their reference sheet row (fr_dmx_bstats_*, BarcodeStats below).
 `--validate` (both modes): the same pass checks every record pair before it is routed -- four lines, '@', '+', equal
 sequence and quality lengths, equal read names and barcodes in both mates -- on the GPU (fr_dmx_validate_*, Validate
 below), and the host checks that neither mate has records left after the other's last; the first bad pair ends the run.
+
+`--single-end` (both modes, every flag above): every input file is a run of its own, its records' codes are their own
+headers', and each output gets an R1 file alone -- the R1 files of the pair (F, a byte copy of F).  The device runs
+with one mate (fr_dmx_set_mates(1)) and the window loop below with one window.
 """
 from __future__ import annotations
 
@@ -44,7 +48,8 @@ import numpy as np
 
 from . import _lib
 from .host import (barcode_stats_path, cycle_stats_path, demux_mode, get_indexes, gz_format, gz_reader, input_spec, limits_of,
-                   mismatch_limits, num_subs_of, parse_files, report_args, single_index, stats_path, validate_flag)
+                   mismatch_limits, num_subs_of, parse_files, report_args, single_end, single_end_inputs, single_index,
+                   stats_path, validate_flag)
 
 RESULTS_HEADER = ["idx1", "idx2", "reads", "matched_idx1", "matched_idx2", "read_type", "sample_name"]
 # the column order `scan` itself writes (frender.py:482-501, report_analysis)
@@ -265,9 +270,12 @@ def writer_kind(name: str, fmt: str = "gzip"):
     return _WRITERS[name]
 
 
-def open_files(name, out_dir, infix, level, kind=_GzDevice):
-    """frender.py:667-676."""
-    return {read: kind(out_path(name, out_dir, infix, read), level) for read in ("R1", "R2")}
+READS = ("R1", "R2")  # a pair's reads; a single-end input (`--single-end`) has the first alone
+
+
+def open_files(name, out_dir, infix, level, kind=_GzDevice, reads=READS):
+    """frender.py:667-676, for the reads that exist."""
+    return {read: kind(out_path(name, out_dir, infix, read), level) for read in reads}
 
 
 _MATE_TAG = re.compile("_R([12])_")
@@ -902,9 +910,10 @@ class Stats:
     the sequence and its fourth the quality -- and this object turns the sums into the CSV: two rows (R1, R2) per
     planned destination, in plan_destinations' order, a sample without reads included."""
 
-    def __init__(self, path=None):
+    def __init__(self, path=None, reads=READS):
         self.path = None if path is None else str(path)
         self.n_dest = 0
+        self.reads = tuple(reads)  # the reads with rows
 
     def begin(self, dmx, n_dest: int):
         self.n_dest = int(n_dest)
@@ -924,8 +933,9 @@ class Stats:
         return np.sum([np.asarray(a, dtype=np.uint64) for a in arrays], axis=0, dtype=np.uint64)
 
     @staticmethod
-    def rows(names, array) -> list:
-        """The CSV's rows without the header.  quality_sum = quality_raw_sum - 33 * quality_bytes (Phred+33; it is
+    def rows(names, array, reads=READS) -> list:
+        """The CSV's rows without the header, for the reads that exist (`--single-end`: R1, whose half of the array
+        is the only one with counts).  quality_sum = quality_raw_sum - 33 * quality_bytes (Phred+33; it is
         negative when the bytes are below '!'); a derived column whose denominator is 0 is left empty."""
         a = np.asarray(array)
         assert a.shape == (2, len(names), len(STATS_FIELDS)), "stats: the array is not [2, destinations, 5]"
@@ -936,18 +946,18 @@ class Stats:
         out = []
         totals = [sum(int(v) for v in a[m, :, 0]) for m in (0, 1)]
         for k, name in enumerate(names):
-            for m, read in enumerate(("R1", "R2")):
-                reads, bases, qbytes, q30, raw = (int(v) for v in a[m, k])
+            for m, read in enumerate(reads):
+                n_reads, bases, qbytes, q30, raw = (int(v) for v in a[m, k])
                 qsum = raw - 33 * qbytes
-                out.append([name, read, reads, bases, q30, qbytes, qsum, ratio(qsum, qbytes), ratio(q30, qbytes, 100),
-                            ratio(reads, totals[m], 100)])
+                out.append([name, read, n_reads, bases, q30, qbytes, qsum, ratio(qsum, qbytes), ratio(q30, qbytes, 100),
+                            ratio(n_reads, totals[m], 100)])
         return out
 
     def write(self, path, names, array):
         with open(path, "w", newline="") as f:
             w = csv.writer(f)
             w.writerow(STATS_HEADER)
-            w.writerows(self.rows(names, array))
+            w.writerows(self.rows(names, array, self.reads))
 
     def write_ranks(self, group, wire, array, names):
         """`--gpus N`, no rank failed: every rank's sums go to rank 0, which adds them and writes the file."""
@@ -974,10 +984,11 @@ class CycleStats:
     the rows of cycles 1..C, C being the last cycle at which any output of that mate has a count, then one row for
     all cycles past max_cycles if any output has one."""
 
-    def __init__(self, path=None, max_cycles: int = MAX_CYCLES):
+    def __init__(self, path=None, max_cycles: int = MAX_CYCLES, reads=READS):
         self.path = None if path is None else str(path)
         self.max_cycles = int(max_cycles)
         self.n_dest = 0
+        self.reads = tuple(reads)  # the reads with rows
 
     def begin(self, dmx, n_dest: int):
         self.n_dest = int(n_dest)
@@ -998,10 +1009,10 @@ class CycleStats:
         return np.sum([np.asarray(a, dtype=np.uint64) for a in arrays], axis=0, dtype=np.uint64)
 
     @staticmethod
-    def rows(names, array) -> list:
-        """The CSV's rows without the header; array [2, len(names), max_cycles + 1, 9].  quality_sum =
-        quality_raw_sum - 33 * quality_bytes (Phred+33; it is negative when the bytes are below '!'); a derived column
-        whose denominator is 0 is left empty."""
+    def rows(names, array, reads=READS) -> list:
+        """The CSV's rows without the header, for the reads that exist; array [2, len(names), max_cycles + 1, 9].
+        quality_sum = quality_raw_sum - 33 * quality_bytes (Phred+33; it is negative when the bytes are below '!'); a
+        derived column whose denominator is 0 is left empty."""
         a = np.asarray(array)
         assert a.ndim == 4 and a.shape[:2] == (2, len(names)) and a.shape[3] == len(CYCLE_FIELDS) and a.shape[2] >= 2, \
             "cycle stats: the array is not [2, destinations, max_cycles + 1, 9]"
@@ -1016,7 +1027,7 @@ class CycleStats:
         tail = [bool(a[m, :, mc].any()) for m in (0, 1)]
         out = []
         for k, name in enumerate(names):
-            for m, read in enumerate(("R1", "R2")):
+            for m, read in enumerate(reads):
                 bins = [(c, str(c + 1)) for c in range(last[m])] + ([(mc, f"{mc + 1}+")] if tail[m] else [])
                 for c, label in bins:
                     v = [int(x) for x in a[m, k, c]]
@@ -1030,7 +1041,7 @@ class CycleStats:
         with open(path, "w", newline="") as f:
             w = csv.writer(f)
             w.writerow(CYCLE_HEADER)
-            w.writerows(self.rows(names, array))
+            w.writerows(self.rows(names, array, self.reads))
 
     def write_ranks(self, group, wire, array, names):
         """`--gpus N`, no rank failed: every rank's counts go to rank 0, which adds them and writes the file."""
@@ -1148,11 +1159,12 @@ class Validate:
     @staticmethod
     def message(r1: str, r2: str, k: int, kind: int, rec1: bytes = b"", rec2: bytes = b"", left: int = 0) -> str:
         """The error of pair k (1-based in the file pair r1 / r2) with violation `kind`; rec1, rec2: the mates' records
-        (kinds 1-10); left: the read (1 or 2) that has records left (kind 11)."""
+        (kinds 1-10); left: the read (1 or 2) that has records left (kind 11).  r2 None: the one-name form, record k
+        of the single-end file r1 (`--single-end`: kinds 1-4 of read 1 are all there is)."""
         def text(b):
             return b.decode("utf-8", "replace")
 
-        head = f"demux --validate: {r1} / {r2}, record {k}: "
+        head = f"demux --validate: {r1}, record {k}: " if r2 is None else f"demux --validate: {r1} / {r2}, record {k}: "
         if kind == V_COUNT:
             return head + f"read {left} has records left after read {3 - left}'s last"
         h1, h2 = rec1.split(b"\n")[0], rec2.split(b"\n")[0]
@@ -1172,33 +1184,36 @@ class Validate:
         return head + f"read {m} sequence has {len(pieces[1])} bases, its quality line {len(pieces[3])} bytes"
 
 
-def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of, writers, window, sheet=None,
+def _demux_pair(dmx, pool, gz, first_index, files, results, route_of, writers, window, sheet=None,
                 hit=None, report=None, stats=None, cycles=None, bstats=None, validate=None, reader=None):
-    """One R1/R2 pair in record-aligned windows: the GPU indexes both windows, the complete
-    record pairs are routed, and the bytes after the last routed record carry into the next
-    window.  Pairing stops when either mate runs out of records (zip, frender.py:777).  The mates
-    inflate on the native pool gz (files i1, i2).  sheet (SheetMode): `demux -b`, no results; hit: a set
+    """One input -- `files`: an R1/R2 pair, or the one file of a single-end input (`--single-end`: dmx is in
+    one-mate mode) -- in record-aligned windows: the GPU indexes the mates' windows, the complete
+    records (record pairs) are routed, and the bytes after the last routed record carry into the next
+    window.  The code mate is the last one: R2 of a pair (frender.py:778), the file itself of a single-end
+    input.  Pairing stops when either mate runs out of records (zip, frender.py:777).  The mates
+    inflate on the native pool gz (files first_index, first_index + 1).  sheet (SheetMode): `demux -b`, no results;
+    hit: a set
     that collects the destinations pairs were routed to; report (Report, after its begin_pair): `--report`, every
     routed window is counted; stats (Stats, after its begin): `--stats`, every routed window is summed; cycles
     (CycleStats, after its begin): `--cycle-stats`, every routed window is counted per cycle; bstats (BarcodeStats,
     after its begin, with sheet): `--barcode-stats`, every routed window is counted per mismatch bin pair; validate
     (Validate, after its begin): `--validate`, every window's pairs are checked before they are routed, the earlier of
     the first bad pair and the route's first error is raised (the bad pair at a tie: a malformed record's code means
-    nothing), and at the end neither mate may have a record left.  reader (GpuReader): `--gz-reader gpu`, i1 and i2
-    are positions in its paths and a BGZF mate's windows are filled on the device."""
-    mates = [os.path.basename(str(read1_file)), os.path.basename(str(read2_file))]
+    nothing), and at the end neither mate may have a record left.  reader (GpuReader): `--gz-reader gpu`, first_index
+    on are positions in its paths and a BGZF mate's windows are filled on the device."""
+    mates = [os.path.basename(str(f)) for f in files]
+    ms = range(len(files))
+    cm = len(files) - 1  # the code mate
     n_routed = 0  # pairs routed so far: --validate's record numbers count from the file pair's first
-    if reader is None:
-        wins_in = [_HostWindow(0, text_chunks(read1_file, gz, i1)), _HostWindow(1, text_chunks(read2_file, gz, i2))]
-    else:
-        wins_in = []
-        try:
-            for m, (f, i) in enumerate(((read1_file, i1), (read2_file, i2))):
-                wins_in.append(reader.window(dmx, m, f, gz, i))
-        except BaseException:
-            for w in wins_in:
-                w.close()
-            raise
+    wins_in = []
+    try:
+        for m, f in enumerate(files):
+            wins_in.append(_HostWindow(m, text_chunks(f, gz, first_index + m)) if reader is None else
+                           reader.window(dmx, m, f, gz, first_index + m))
+    except BaseException:
+        for w in wins_in:
+            w.close()
+        raise
     pending = []  # the previous window's gzip jobs: overlap with this window's inflate and GPU work
     st, clock = STAGE_TIMES, time.perf_counter
     try:
@@ -1207,14 +1222,14 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
             for w in wins_in:
                 w.read(window)
             t1 = clock()
-            n = [wins_in[0].load(dmx, window), wins_in[1].load(dmx, window)]
+            n = [w.load(dmx, window) for w in wins_in]
             eof = [w.host.eof if getattr(w, "host", None) is not None else w.eof for w in wins_in]
             t2 = clock()
             # the last record of a window may continue in the next one unless its file ended
-            done = [n[m] if eof[m] else max(n[m] - 1, 0) for m in (0, 1)]
+            done = [n[m] if eof[m] else max(n[m] - 1, 0) for m in ms]
             n_pairs = min(done)
             if n_pairs == 0:
-                if (eof[0] and not n[0]) or (eof[1] and not n[1]):  # a mate is out of records
+                if any(eof[m] and not n[m] for m in ms):  # a mate is out of records
                     break
                 window *= 2  # a record longer than the window: widen it
                 continue
@@ -1223,8 +1238,8 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
             ex = dmx.exotic(n_pairs)
             codes = []
             if ex.size:  # codes outside the fast alphabet: resolve by string
-                starts, _ = dmx.records(1, ex)
-                codes = [_code_of(ln) for ln in wins_in[1].lines_at(dmx, starts.tolist())]
+                starts, _ = dmx.records(cm, ex)
+                codes = [_code_of(ln) for ln in wins_in[cm].lines_at(dmx, starts.tolist())]
                 dest = sheet.resolve(codes) if sheet is not None else \
                     [route_of(results[c]) if c in results else _lib.FR_DMX_MISSING for c in codes]
                 dmx.patch(ex, np.array(dest, dtype=np.int32))
@@ -1235,11 +1250,12 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
             if validate is not None:
                 bad, kind = validate.result(dmx)
                 if bad >= 0 and (first < 0 or bad <= first):  # the earlier pair; at the same pair the validation
-                    recs = [wins_in[m].span(dmx, *(int(v[0]) for v in dmx.records(m, [bad]))) for m in (0, 1)]
-                    raise SystemExit(Validate.message(*mates, n_routed + bad + 1, kind, *recs))
+                    recs = [wins_in[m].span(dmx, *(int(v[0]) for v in dmx.records(m, [bad]))) for m in ms]
+                    raise SystemExit(Validate.message(mates[0], mates[1] if cm else None, n_routed + bad + 1, kind,
+                                                      *recs))
             if first >= 0:
-                s, _ = dmx.records(1, [first])
-                code = _code_of(wins_in[1].line_at(dmx, int(s[0])))
+                s, _ = dmx.records(cm, [first])
+                code = _code_of(wins_in[cm].line_at(dmx, int(s[0])))
                 if val == _lib.FR_DMX_MISSING:
                     raise SystemExit(f"Couldn't find barcode {code} in supplied frender result file!")
                 err = sheet.error(code, val) if sheet is not None else None
@@ -1258,14 +1274,15 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 hit.update(np.nonzero(b1 + b2)[0].tolist())
             n_routed += n_pairs
             # each mate's bytes for the files and their per-destination sizes, as the writers' family makes them
-            wins = [type(writers[0]["R1"]).window(dmx, m, len(writers), b) for m, b in ((0, b1), (1, b2))]
+            routed_of = (b1, b2)[:len(files)]
+            wins = [type(writers[0]["R1"]).window(dmx, m, len(writers), b) for m, b in enumerate(routed_of)]
             t4 = clock()
             for j in pending:
                 j.result()
             cums = [np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64) for _, sizes, _ in wins]
             pending = []
             for k, w in enumerate(writers):
-                for (arr, _, extras), c, routed, read in zip(wins, cums, (b1, b2), ("R1", "R2")):
+                for (arr, _, extras), c, routed, read in zip(wins, cums, routed_of, READS):
                     if routed[k]:
                         pending.append(pool.submit(w[read].write, arr, int(c[k]), int(c[k + 1]),
                                                    *(extras[k] if extras else ())))
@@ -1275,15 +1292,15 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
                 st[k] = st.get(k, 0.0) + v
             st["windows"] = st.get("windows", 0) + 1
             # carry the bytes after the routed records
-            for m in (0, 1):
+            for m in ms:
                 if n_pairs < n[m]:
                     s, _ = dmx.records(m, [n_pairs])
                     wins_in[m].carry(int(s[0]))
                 else:
                     wins_in[m].carry(None)
-            if (eof[0] and n_pairs == n[0]) or (eof[1] and n_pairs == n[1]):
+            if any(eof[m] and n_pairs == n[m] for m in ms):
                 break
-        if validate is not None:
+        if validate is not None and cm:
             # a mate has a record left if it holds a byte past the routed records, or its stream yields one more
             more = [w.has_more(dmx) for w in wins_in]
             if more[0] != more[1]:
@@ -1294,31 +1311,39 @@ def _demux_pair(dmx, pool, gz, i1, i2, read1_file, read2_file, results, route_of
         for w in wins_in:
             w.close()
         if reader is not None:
-            for m in (0, 1):
+            for m in ms:
                 dmx.bgzf_close(m)
 
 
-def _drop_unhit(names, lazy, hit, out_dir, infix) -> None:
+def _drop_unhit(names, lazy, hit, out_dir, infix, reads=READS) -> None:
     """`demux -b`: a sample's file pair exists iff a pair was routed to it, as in -r mode, where the sample
     ids come from the results.  The writers were opened for every sheet id: remove the pairs of the ids in
-    `lazy` that `hit` lacks (after their writers are closed)."""
+    `lazy` that `hit` lacks (after their writers are closed).  reads: the reads that exist."""
     for k in sorted(lazy - hit):
-        for read in ("R1", "R2"):
+        for read in reads:
             with contextlib.suppress(FileNotFoundError):
                 os.unlink(out_path(names[k], out_dir, infix, read))
 
 
-def _close_writers(writers, names, lazy, hit, out_dir, infix) -> None:
+def _close_writers(writers, names, lazy, hit, out_dir, infix, reads=READS) -> None:
     """Close a destination list's writer pairs in out_dir, then drop the sample pairs nothing was routed to."""
     for w in writers:
         for f in w.values():
             f.close()
-    _drop_unhit(names, lazy, hit, out_dir, infix)
+    _drop_unhit(names, lazy, hit, out_dir, infix, reads)
+
+
+def _switch_mates(dmx, n_from: int, n_to: int):
+    """dmx from n_from mates per input to n_to (Demux.set_mates), between inputs: the count changes only with no
+    window at hand, so the mates that exist are emptied first."""
+    for m in range(n_from):
+        dmx.load_parts(m, [])
+    dmx.set_mates(n_to)
 
 
 @contextlib.contextmanager
 def _session(t_start, paths, kind, n_dest, device, sheet, table, dev=None, ctx=None, finish=None, gz_reader="host",
-             reader_chunk=0):
+             reader_chunk=0, n_mates=2):
     """What one process demultiplexes with, on one GPU or as a rank of N: (dmx, pool, gz, reader).  reader is None
     unless gz_reader is "gpu": then a GpuReader over `paths`, and gz holds only the files that one leaves to the
     host (None when it leaves none), so no host thread inflates a file the GPU reader takes.  gz, the inflate
@@ -1327,9 +1352,11 @@ def _session(t_start, paths, kind, n_dest, device, sheet, table, dev=None, ctx=N
     comes up.  dmx is the caller's `dev` or a Demux of `device`, bound to the sheet (on the caller's `ctx`, if
     any) or to the results' `table` (keys, vals); pool runs the writers' jobs.  The way out, in one order:
     inflate pool, writer pool, finish() (the caller's writers), the device (a caller's `dev` stays open),
-    the sheet context.  STAGE_TIMES gets its setup and finish entries (t_start: when the command began)."""
+    the sheet context.  STAGE_TIMES gets its setup and finish entries (t_start: when the command began).  n_mates 1
+    (`--single-end`): dmx is put into one-mate mode, and a caller's `dev` goes back in pair mode."""
     st, clock = STAGE_TIMES, time.perf_counter
     gz = dmx = pool = None
+    one_mate = False
     try:
         nt = _inflate_threads(kind)
         reader = GpuReader(paths, nt, reader_chunk) if gz_reader == "gpu" else None
@@ -1340,6 +1367,9 @@ def _session(t_start, paths, kind, n_dest, device, sheet, table, dev=None, ctx=N
         st["setup: results, writers"] = clock() - t_start
         dmx = dev or _lib.Demux(device)
         pool = ThreadPoolExecutor(max_workers=max(2, min(32, n_dest * 2)))
+        if n_mates == 1:
+            _switch_mates(dmx, 2 if dev is not None else 0, 1)  # (a Demux of our own holds no window yet)
+            one_mate = True
         if sheet is not None:
             sheet.bind(dmx, device, ctx)
         else:
@@ -1359,8 +1389,11 @@ def _session(t_start, paths, kind, n_dest, device, sheet, table, dev=None, ctx=N
         t_files = clock()
         if dmx is not None and dev is None:
             dmx.close()
-        elif dmx is not None and sheet is not None:
-            dmx.set_table(np.zeros(0, np.uint64), np.zeros(0, np.int32))  # end the borrow of the sheet context
+        elif dmx is not None:
+            if one_mate:  # a caller's dev goes back as it came: in pair mode
+                _switch_mates(dmx, 1, 2)
+            if sheet is not None:
+                dmx.set_table(np.zeros(0, np.uint64), np.zeros(0, np.int32))  # end the borrow of the sheet context
         if sheet is not None:
             sheet.close()
         st.update({"finish: inflate pool": t_gz - t_end, "finish: writer pool": t_pool - t_gz,
@@ -1383,6 +1416,8 @@ def frender_demux(args, dev=None, ctx=None) -> None:
     fmt = gz_format(args)
     gz_reader(args)  # refused here if it is neither host nor gpu, before anything is created
     single = single_index(args)
+    n_mates = 1 if single_end(args) else 2  # --single-end: every kept file is an input of its own
+    reads = READS[:n_mates]
     num_subs = num_subs_of(*mismatch_limits(args)) if mode == "b" else None  # --n2 with --single-index: refused here
     samples = not args.no_samples
     level = getattr(args, "gz_level", None) or 9  # gzip.open's default, as the reference writes
@@ -1409,19 +1444,22 @@ def frender_demux(args, dev=None, ctx=None) -> None:
         indexes = get_indexes(Path(args.b), single)
         ids = sorted(set(indexes["id"]) - {""})
 
+    inputs = None
+    if n_mates == 1:  # a read pair among the files is refused before anything is created
+        inputs = single_end_inputs(parse_files(input_spec(args.files), just_r1=False))
     if group is None:
         os.mkdir(args.d)
     else:
         _mkdir_everywhere(group, args.d)
     names, route_of = plan_destinations(ids, samples, not args.no_undeter, not args.no_index_hop, not args.no_ambiguous)
     # destination id -> writer pair (N ranks: its name; rank 0 writes the files at the end)
-    writers = [open_files(name, args.d, infix, level, kind) for name in names] if group is None else names
+    writers = [open_files(name, args.d, infix, level, kind, reads) for name in names] if group is None else names
     sheet = SheetMode(indexes, num_subs, route_of, single) if mode == "b" else None
     lazy = set(range(len(ids))) if sheet is not None and samples else set()  # sample destinations (-b: kept if hit)
     hit = set()
     report = Report(report_path, prefix) if report_path is not None else None  # --report (with -b: report_args)
-    stats = Stats(stats_file) if stats_file is not None else None  # --stats
-    cycles = CycleStats(cycles_file) if cycles_file is not None else None  # --cycle-stats
+    stats = Stats(stats_file, reads) if stats_file is not None else None  # --stats
+    cycles = CycleStats(cycles_file, reads=reads) if cycles_file is not None else None  # --cycle-stats
     bstats = BarcodeStats(bstats_file) if bstats_file is not None else None  # --barcode-stats (with -b)
     validate = Validate() if validate_flag(args) else None  # --validate
 
@@ -1431,17 +1469,18 @@ def frender_demux(args, dev=None, ctx=None) -> None:
         keys, fast = _lib.pack_fast(codes)
         table = keys[fast], np.array([route_of(results[c]) for c in codes], dtype=np.int32)[fast]
 
-    pairs = get_paired_files(parse_files(input_spec(args.files), just_r1=False))
+    # the inputs: file pairs (R1, R2), or with --single-end one-file tuples
+    pairs = inputs if inputs is not None else get_paired_files(parse_files(input_spec(args.files), just_r1=False))
 
     window = int(getattr(args, "window", None) or (512 << 20))  # decoded bytes per mate per GPU pass
     if group is not None:
         return _demux_ranks(group, args, pairs, results, route_of, table, writers, window, level, infix, kind, sheet,
-                            lazy, t_start, report, stats, cycles, bstats, validate)
+                            lazy, t_start, report, stats, cycles, bstats, validate, reads)
     paths = [str(f) for pr in pairs for f in pr]
     try:
         with _session(t_start, paths, kind, len(writers), _device_index(None), sheet, table, dev, ctx,
-                      lambda: _close_writers(writers, names, lazy, hit, args.d, infix), gz_reader(args),
-                      int(getattr(args, "gz_reader_chunk", 0) or 0)) as (dmx, pool, gz, reader):
+                      lambda: _close_writers(writers, names, lazy, hit, args.d, infix, reads), gz_reader(args),
+                      int(getattr(args, "gz_reader_chunk", 0) or 0), n_mates) as (dmx, pool, gz, reader):
             if report is not None:
                 report.begin(dmx)
             if stats is not None:
@@ -1453,21 +1492,23 @@ def frender_demux(args, dev=None, ctx=None) -> None:
             if validate is not None:
                 validate.begin(dmx)
             try:
-                for k, (read1_file, read2_file) in enumerate(pairs):
-                    print(f"Demultiplexing {read1_file.name}...")
+                for k, files in enumerate(pairs):
+                    print(f"Demultiplexing {files[0].name}...")
                     if report is not None:
                         report.begin_pair(dmx, k)
-                    _demux_pair(dmx, pool, gz, 2 * k, 2 * k + 1, read1_file, read2_file, results, route_of, writers,
+                    _demux_pair(dmx, pool, gz, n_mates * k, files, results, route_of, writers,
                                 window, sheet, hit, report, stats, cycles, bstats, validate, reader)
             finally:
                 if reader is not None:
-                    READER_INFO.update({"R1": dmx.bgzf_info(0), "R2": dmx.bgzf_info(1)})
+                    if n_mates == 1:  # (a pair's two keys are overwritten below: only here can R2's be stale)
+                        READER_INFO.pop("R2", None)
+                    READER_INFO.update({read: dmx.bgzf_info(m) for m, read in enumerate(reads)})
                 if validate is not None:  # a caller's dev goes back as it came: the validation off
                     validate.end(dmx)
             if sheet is not None and samples and not (hit & lazy):
                 print(NO_SAMPLES_WARNING)  # known only now: no pair was demuxable
             if report is not None:  # every pair is routed: the table is complete
-                report.write_local(dmx, sheet, [str(os.path.basename(r1)) for r1, _ in pairs])
+                report.write_local(dmx, sheet, [str(os.path.basename(fs[0])) for fs in pairs])
             if stats is not None:
                 print(f"Writing demux statistics to {stats.path}")
                 stats.write(stats.path, names, stats.local(dmx))
@@ -1535,7 +1576,7 @@ def _mkdir_everywhere(group, path):
 
 
 def _demux_ranks(group, args, pairs, results, route_of, table, names, window, level, infix, kind, sheet, lazy,
-                 t_start, report=None, stats=None, cycles=None, bstats=None, validate=None):
+                 t_start, report=None, stats=None, cycles=None, bstats=None, validate=None, reads=READS):
     import shutil
 
     from .dist import PeerFailed, reduce_min
@@ -1552,7 +1593,8 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
         # (-b: this rank's own sheet context: classification is stateless, nothing is exchanged)
         with _session(t_start, [str(f) for k in mine for f in pairs[k]], kind, len(names), _device_index(group),
                       sheet, table, gz_reader=gz_reader(args),
-                      reader_chunk=int(getattr(args, "gz_reader_chunk", 0) or 0)) as (dmx, pool, gz, reader):
+                      reader_chunk=int(getattr(args, "gz_reader_chunk", 0) or 0),
+                      n_mates=len(reads)) as (dmx, pool, gz, reader):
             if report is not None:
                 report.begin(dmx)
             if stats is not None:
@@ -1566,17 +1608,19 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
             for j, k in enumerate(mine):
                 d = os.path.join(parts, str(k))
                 os.makedirs(d, exist_ok=True)
-                writers = [open_files(n, d, infix, level, _BgzfPart if kind is _BgzfDevice else kind) for n in names]
+                writers = [open_files(n, d, infix, level, _BgzfPart if kind is _BgzfDevice else kind, reads)
+                           for n in names]
                 hit = set()
                 try:
                     if report is not None:
                         report.begin_pair(dmx, k)  # the global pair index: the ordinals are the one-process run's
-                    _demux_pair(dmx, pool, gz, 2 * j, 2 * j + 1, pairs[k][0], pairs[k][1], results, route_of, writers,
+                    _demux_pair(dmx, pool, gz, len(reads) * j, pairs[k], results, route_of, writers,
                                 window, sheet, hit, report, stats, cycles, bstats, validate, reader)
                 except (Exception, SystemExit) as e:  # re-raised below if it is the first in pair order
                     failed, exc = k, e
                 finally:
-                    _close_writers(writers, names, lazy, hit, d, infix)  # -b: no part for a sample without reads here
+                    # (-b: no part for a sample without reads here)
+                    _close_writers(writers, names, lazy, hit, d, infix, reads)
                 if exc is not None:
                     break
             if report is not None and exc is None:
@@ -1597,7 +1641,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
             print(f"Demultiplexing {pairs[k][0].name}...")
         any_sample = False
         for i, n in enumerate(names):
-            for read in ("R1", "R2"):
+            for read in reads:
                 final = out_path(n, args.d, infix, read)
                 if i in lazy:  # -b: a sample's files exist iff some pair has a part for it (_drop_unhit)
                     if not any(os.path.exists(out_path(n, os.path.join(parts, str(k)), infix, read))
@@ -1624,7 +1668,7 @@ def _demux_ranks(group, args, pairs, results, route_of, table, names, window, le
             raise exc
         raise PeerFailed()
     if report is not None:  # no rank failed: every rank has its table
-        report.write_ranks(group, _wire(group), tally, [str(os.path.basename(r1)) for r1, _ in pairs], sheet,
+        report.write_ranks(group, _wire(group), tally, [str(os.path.basename(fs[0])) for fs in pairs], sheet,
                            _device_index(group))
     if stats is not None:  # after the output files are assembled, and after everything else the command prints
         if rank == 0:

@@ -166,6 +166,40 @@ def parse_files(file_dict: dict, just_r1: bool) -> list:
     return kept
 
 
+def single_end(args) -> bool:
+    """--single-end of a demux's arguments (a namespace without the field, as the reference's, means paired)."""
+    return bool(getattr(args, "single_end", False))
+
+
+def read_mates(a: str, b: str):
+    """(read 1, read 2) when the two paths are read mates -- equal length, different in exactly one position, where
+    one has `1` and the other `2` directly after `_R` and directly before `_` -- else None.  Names without the
+    token are simply no mates (demux.is_read_mate raises on them, as the reference does)."""
+    if len(a) != len(b):
+        return None
+    diff = [k for k in range(len(a)) if a[k] != b[k]]
+    if len(diff) != 1:
+        return None
+    k = diff[0]
+    if {a[k], b[k]} != {"1", "2"} or k < 2 or a[k - 2:k] != "_R" or a[k + 1:k + 2] != "_":
+        return None
+    return (a, b) if a[k] == "1" else (b, a)
+
+
+def single_end_inputs(kept) -> list:
+    """`demux --single-end`: the kept files (parse_files' list) as inputs, one one-file tuple each, in that order.
+    A read pair among them is refused: its R2 would be demultiplexed as a run of its own."""
+    paths = [str(p) for p in kept]
+    for i, a in enumerate(paths):
+        for b in paths[i + 1:]:
+            mates = read_mates(a, b)
+            if mates is not None:
+                r1, r2 = (os.path.basename(m) for m in mates)
+                raise SystemExit(f"demux --single-end: {r1} and {r2} are read 1 and read 2 of one run; demultiplex "
+                                 "pairs without --single-end")
+    return [(p,) for p in kept]
+
+
 def reverse_complement(s: str) -> str:
     """frender.py:210-211."""
     return s.translate(str.maketrans("ATGCNatgcn", "TACGNtacgn"))[::-1]

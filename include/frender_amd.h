@@ -392,6 +392,20 @@ int fr_dmx_set_sheet(fr_dmx* d, fr_ctx* ctx, int num_subs, const int32_t* row_de
  * fr_dmx_set_sheet(n) is fr_dmx_set_sheet2(n, n) */
 int fr_dmx_set_sheet2(fr_dmx* d, fr_ctx* ctx, int num_subs1, int num_subs2, const int32_t* row_dest, int n_rows,
                       const int32_t class_dest[4]);
+/* The mates of an input: 2 (the default: a read pair, mate 1 is the code mate) or 1, a single-end file
+ * (`demux --single-end`).  With 1 there is no mate 1: mate 0 is the code mate, so fr_dmx_load* / fr_dmx_bgzf_fill
+ * with mate 0 do what they do with mate 1 of a pair (count and index the records, extract every record's code: the
+ * table lookup, or in sheet mode the fast key, the classification and with fr_dmx_bstats_begin the bin byte), and
+ * fr_dmx_exotic / _patch / _bstats_patch / _tally_window index mate 0's records.  fr_dmx_route routes
+ * min(n_pairs, mate 0's records) records with one length pass, one offset scan and one copy; every bytes_r2[k] is 0
+ * and nothing of mate 1's is allocated or touched.  fr_dmx_stats_window / _cycles_window launch over one mate (the
+ * accumulators keep their layout, mate 1's half stays zero); fr_dmx_validate_window needs mate 0 alone and checks
+ * kinds 1-4 of its records.  Every entry point that takes a mate returns FR_ERR_INVALID for mate 1.
+ * n_mates outside {1, 2} is FR_ERR_INVALID; a call that changes nothing is a no-op (so fr_dmx_set_mates(2) on a new
+ * context is); a call that changes the count is FR_ERR_INVALID while a mate holds a window (the last fr_dmx_load* or
+ * fill of a mate left bytes: a load of zero bytes empties it) or a BGZF mate is open.  A caller that borrowed a
+ * context sets it back to 2 once its last window is done, as it calls fr_dmx_validate_end. */
+int fr_dmx_set_mates(fr_dmx* d, int n_mates);
 /* mate 0 = R1, 1 = R2 (R2 also resolves every record's destination); returns the record count */
 int fr_dmx_load(fr_dmx* d, int mate, const uint8_t* data, uint64_t len, uint64_t* n_records);
 /* the same over the concatenation of n_parts host buffers (a window without a host-side join) */

@@ -21,7 +21,9 @@ flag; its output files are compared with the one-pass run's.  With --cycle-stats
 the rounds in the same way: the flag's cost is its difference to `demux -b` on this tree, and with --parent the
 parent's `demux -b` is timed in the same rounds, which this tree's must equal without the flag.  With
 --barcode-stats-arm, `demux -b --barcode-stats` joins the rounds in the same way, and with --validate-arm `demux -b
---validate`.  Writes one JSON
+--validate`.  With --single-end-arm the R1 files are also paired with byte copies of themselves as R2 and three more
+commands join the rounds: (a) `demux -b --single-end` on the R1 files, (b) `demux -b` on the (R1, copy) pairs on this
+tree and, with --parent, (c) the same at the parent commit; (a)'s files must be (b)'s R1 files.  Writes one JSON
 document (--out), stamped with the tree's source hash.
 
 Needs a GPU: there is no CPU path to time.
@@ -101,6 +103,9 @@ def main():
     ap.add_argument("--validate-arm", action="store_true",
                     help="also time demux -b --validate (every pair checked before it is routed, same pass) and, with "
                          "--parent, the parent's demux -b in the same rounds")
+    ap.add_argument("--single-end-arm", action="store_true",
+                    help="also time demux -b --single-end on the R1 files against demux -b on the same files paired "
+                         "with byte copies as R2, on this tree and, with --parent, at the parent commit")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "demux_sheet_bench.json"))
     ap.add_argument("--workdir", help="where the inputs and outputs go (default: a temporary directory)")
     args = ap.parse_args()
@@ -200,6 +205,32 @@ def main():
             shutil.rmtree(w)
             return {"total_s": t, "stages": st}
 
+        copy_all = copy_r1 = []
+        if args.single_end_arm:  # (R1, a byte copy of R1 named as its R2)
+            cp = os.path.join(d, "in_copy")
+            os.makedirs(cp, exist_ok=True)
+            for f in r1:
+                shutil.copy(f, os.path.join(cp, os.path.basename(f)))
+                shutil.copy(f, os.path.join(cp, os.path.basename(f).replace("_R1_", "_R2_")))
+            copy_all = sorted(os.path.join(cp, x) for x in os.listdir(cp))
+            copy_r1 = [f for f in copy_all if "_R1_" in f]
+
+        def single_pass():
+            serial[0] += 1
+            w = os.path.join(d, f"se_{serial[0]}")
+            os.mkdir(w)
+            t, st = run(["demux", "-b", sheet_csv, "-n", "1", "--single-end", "-d", os.path.join(w, "out"), "--stage-times",
+                         *copy_r1], w, ROOT)
+            return {"total_s": t, "stages": st, "dir": w}
+
+        def copy_pair_pass(root=ROOT):
+            serial[0] += 1
+            w = os.path.join(d, f"cpy_{serial[0]}")
+            os.mkdir(w)
+            t, st = run(["demux", "-b", sheet_csv, "-n", "1", "-d", os.path.join(w, "out"), "--stage-times", *copy_all], w,
+                        root)
+            return {"total_s": t, "stages": st, "dir": w}
+
         cold = {"two_pass": two_pass(), "one_pass": one_pass()}
         da, db = digests(os.path.join(cold["two_pass"]["dir"], "out")), digests(os.path.join(cold["one_pass"]["dir"], "out"))
         equal = da == db
@@ -238,18 +269,26 @@ def main():
         if args.validate_arm:
             cold["validate"] = validate_pass()
             validate_doc = {"outputs_equal": digests(os.path.join(cold["validate"]["dir"], "out")) == db}
+        single_doc = None
+        if args.single_end_arm:
+            cold["single_end"], cold["copy_pair"] = single_pass(), copy_pair_pass()
+            ds = digests(os.path.join(cold["single_end"]["dir"], "out"))
+            dc = digests(os.path.join(cold["copy_pair"]["dir"], "out"))
+            single_doc = {"outputs_equal_r1_of_pairs": ds == {k: v for k, v in dc.items() if k.endswith("R1.fq.gz")},
+                          "output_files": len(ds), "r2_files": sum(1 for k in ds if "R2" in k)}
         csv_path = os.path.join(d, "results.csv")
         shutil.copy(cold["two_pass"]["csv"], csv_path)
         out_files = len(da)
         for c in cold.values():
             shutil.rmtree(c["dir"])
         warm = {"two_pass": [], "one_pass": [], "report": [], "stats": [], "cycles": [], "bstats": [], "validate": [], "parent_demux_r": [],
-                "parent_one_pass": []}
+                "parent_one_pass": [], "single_end": [], "copy_pair": [], "parent_copy_pair": []}
         arms = (("two_pass", two_pass), ("one_pass", one_pass)) + ((("report", report_pass),) if args.report_arm else ()) \
             + ((("stats", stats_pass),) if args.stats_arm else ()) \
             + ((("cycles", cycles_pass),) if args.cycle_stats_arm else ()) \
             + ((("bstats", bstats_pass),) if args.barcode_stats_arm else ()) \
-            + ((("validate", validate_pass),) if args.validate_arm else ())
+            + ((("validate", validate_pass),) if args.validate_arm else ()) \
+            + ((("single_end", single_pass), ("copy_pair", copy_pair_pass)) if args.single_end_arm else ())
         for _ in range(max(args.runs, 5)):
             for name, fn in arms:
                 r = fn()
@@ -259,6 +298,10 @@ def main():
                 warm["parent_demux_r"].append(demux_r(os.path.abspath(args.parent), csv_path))
                 if args.stats_arm or args.cycle_stats_arm or args.barcode_stats_arm or args.validate_arm:
                     warm["parent_one_pass"].append(parent_one_pass(os.path.abspath(args.parent)))
+                if args.single_end_arm:
+                    r = copy_pair_pass(os.path.abspath(args.parent))
+                    shutil.rmtree(r.pop("dir"))
+                    warm["parent_copy_pair"].append(r)
 
         def strip(r):
             return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items() if k not in ("dir", "csv")}
@@ -361,12 +404,34 @@ def main():
             if warm["parent_one_pass"]:
                 validate_doc["parent_one_pass_total_s"] = spread([r["total_s"] for r in warm["parent_one_pass"]])
             doc["validate_arm"] = validate_doc
+        if single_doc is not None:
+            a_t, b_t = ([r["total_s"] for r in warm[k]] for k in ("single_end", "copy_pair"))
+            c_t = [r["total_s"] for r in warm["parent_copy_pair"]]
+            stage_keys = ("inflate+join", "load+index", "route", "deflate/fetch", "wait writers", "setup", "finish")
+            single_doc.update({
+                "what": "(a) demux -b -n 1 --single-end on the R1 files against (b) demux -b -n 1 on the same files "
+                        "paired with byte copies as R2, on this tree, and (c) the same pairs at the parent commit, in the "
+                        "same alternating rounds",
+                "a_single_end_total_s": spread(a_t), "b_copy_pair_total_s": spread(b_t),
+                "a_over_b": round(statistics.median(a_t) / statistics.median(b_t), 4),
+                "every_a_below_every_b": max(a_t) < min(b_t),
+                "M_records_per_s": {"a": round(n_pairs / statistics.median(a_t) / 1e6, 4),
+                                    "b": round(n_pairs / statistics.median(b_t) / 1e6, 4)},
+                # seconds per run and stage (medians): which stage holds what (a) does not save
+                "stage_s": {name: {k: spread([r["stages"][k] for r in runs]) for k in stage_keys}
+                            for name, runs in (("a", warm["single_end"]), ("b", warm["copy_pair"]),
+                                               ("c", warm["parent_copy_pair"])) if runs}})
+            if c_t:
+                single_doc["c_parent_copy_pair_total_s"] = spread(c_t)
+                single_doc["b_and_c_spreads_overlap"] = min(b_t) <= max(c_t) and min(c_t) <= max(b_t)
+            doc["single_end_arm"] = single_doc
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
             f.write("\n")
         print(json.dumps({k: doc[k] for k in ("tree_hash", "outputs_equal", "warm", "stages_ms_per_window", "report_arm",
-                                                   "stats_arm", "cycle_stats_arm", "barcode_stats_arm", "validate_arm")
+                                                   "stats_arm", "cycle_stats_arm", "barcode_stats_arm", "validate_arm",
+                                                   "single_end_arm")
                           if k in doc}))
         if not equal:
             raise SystemExit("the two routes' outputs differ: " +
