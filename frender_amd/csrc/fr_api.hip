@@ -297,40 +297,55 @@ static int read_state(fr_ctx* ctx) {  // exact snapshot (a host round trip only 
     return FR_OK;
 }
 
-// grow the table (x4) and/or re-insert overflow entries; stream-ordered between launches
+// grow the table (x4) and/or re-insert overflow entries; stream-ordered between launches.  The overflow list is
+// empty when this returns FR_OK: an entry whose GPROBE probe slots are still full after the re-insert (a cluster
+// of codes with neighbouring homes, in a table far from half full) is back on the list, the re-insert's last
+// workgroup says so in the pinned mirror, and the table doubles and takes the list again -- at most GROW_ROUNDS
+// times, then FR_ERR_CAPACITY.  A call without overflow entries queues and waits for nothing more than before.
+constexpr int GROW_ROUNDS = 8;
 static int grow_table(fr_ctx* ctx, bool force_bigger) {
     int rc = read_state(ctx);
     if (rc) return rc;
     const u64 nkeys = ctx->h_st->n_keys;
-    const u64 novf = std::min<u64>(ctx->h_st->n_overflow, ctx->tab.ovf_cap);
-    if (force_bigger || (nkeys + novf) * 2 > ctx->nslots) {
-        u64 ns = ctx->nslots;
-        while ((nkeys + novf) * 4 > ns) ns <<= 1;
-        if (ns == ctx->nslots) ns <<= 1;
-        GSlot* ns_slots = nullptr;
-        CK(dalloc(&ns_slots, ns));
-        CK(launch_table_init(ns_slots, ns, nullptr, ctx->stream));
-        Table t = ctx->tab;
-        t.slots = ns_slots;
-        t.mask = ns - 1;
-        CK(launch_rehash(t, ctx->tab.slots, ctx->nslots, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-        CK(hipFree(ctx->tab.slots));
-        ctx->tab = t;
-        ctx->nslots = ns;
-    }
-    if (novf) {
+    u64 novf = std::min<u64>(ctx->h_st->n_overflow, ctx->tab.ovf_cap);
+    const u64 rows = nkeys + novf;  // (an upper bound of the live keys in every later round)
+    for (int round = 0;; ++round) {
+        if (force_bigger || rows * 2 > ctx->nslots) {
+            u64 ns = ctx->nslots;
+            while (rows * 4 > ns) ns <<= 1;
+            if (ns == ctx->nslots) ns <<= 1;
+            GSlot* ns_slots = nullptr;
+            CK(dalloc(&ns_slots, ns));
+            CK(launch_table_init(ns_slots, ns, nullptr, ctx->stream));
+            Table t = ctx->tab;
+            t.slots = ns_slots;
+            t.mask = ns - 1;
+            CK(launch_rehash(t, ctx->tab.slots, ctx->nslots, ctx->stream));
+            CK(hipStreamSynchronize(ctx->stream));
+            CK(hipFree(ctx->tab.slots));
+            ctx->tab = t;
+            ctx->nslots = ns;
+        }
+        if (!novf) return FR_OK;
         Overflow* old = ctx->tab.ovf;
         Overflow* fresh = nullptr;
         CK(dalloc(&fresh, ctx->tab.ovf_cap));
         ctx->tab.ovf = fresh;
+        ctx->h_mir->ovf_left = 0;
         CK(fill_async(ctx, &ctx->st->n_overflow, 0, sizeof(u64)));
-        CK(launch_reinsert_overflow(ctx->tab, ctx->st, old, novf, ctx->stream));
+        CK(launch_reinsert_overflow(ctx->tab, ctx->st, old, novf, &ctx->d_mir->ovf_left, ctx->stream));
         ctx->st_fresh = false;
         CK(hipStreamSynchronize(ctx->stream));
         CK(hipFree(old));
+        const u64 left = ctx->h_mir->ovf_left;
+        if (!left) return FR_OK;
+        // (the table's slot indices are 32-bit in insert_rows)
+        if (round == GROW_ROUNDS || ctx->nslots >= (1ull << 31))
+            return fail(ctx, FR_ERR_CAPACITY, std::to_string(left) + " codes stay past the probe bound in a table of " +
+                                                  std::to_string(ctx->nslots) + " slots");
+        novf = std::min<u64>(left, ctx->tab.ovf_cap);
+        force_bigger = true;
     }
-    return FR_OK;
 }
 
 // the presence list must take one more entry per live key (appended by the per-file scan)
@@ -1360,7 +1375,7 @@ int fr_end_file(fr_ctx* ctx, fr_file_stats* out) {
     int rc = ctx->host_feed ? settle_exotic(ctx) : FR_OK;  // device feeds settled at their end
     if (rc) return rc;
     ctx->last_valid = false;
-    rc = grow_table(ctx, false);  // re-inserts any overflow; exact state afterwards
+    rc = grow_table(ctx, false);  // re-inserts any overflow, growing until the list is empty: exact state afterwards
     if (rc) return rc;
     // the first file since the reset: every live key is its (it made them all), so its presence scan waits
     // until a second file begins (flush_presence) -- a one-file scan never runs it (fr_finalize)

@@ -165,6 +165,7 @@ struct HostMirror {
     // (a cache line each: the host zeroes a word of its own while another kernel's may still be on its way)
     alignas(64) u64 fin_count;  // fin_scatter_kernel: the bin scan's last entry (every live slot counted once)
     alignas(64) u64 err_flag;   // classify_kernel: nonzero when some code had an error (the host then reads the exact word)
+    alignas(64) u64 ovf_left;   // reinsert_kernel: entries the re-insert put on the overflow list again (grow_table grows on)
 };
 
 struct Table {
@@ -311,7 +312,8 @@ __host__ __device__ inline u32 log_bucket(u64 key) {
 hipError_t launch_table_init(GSlot* slots, u64 n, DevState* st, hipStream_t s);
 hipError_t launch_chunk_scan(const ScanArgs& a, int grid, hipStream_t s);
 int chunk_occupancy();  // tally workgroups per CU the kernel is built for
-hipError_t launch_reinsert_overflow(Table t, DevState* st, const Overflow* src, u64 n, hipStream_t s);
+// left_out (pinned, device-visible): the entries that went past the probe bound again, written by the last workgroup
+hipError_t launch_reinsert_overflow(Table t, DevState* st, const Overflow* src, u64 n, u64* left_out, hipStream_t s);
 hipError_t launch_rehash(Table dst, const GSlot* src, u64 nsrc, hipStream_t s);
 hipError_t launch_compact(const GSlot* slots, u64 nslots, u64* keys, u64* counts, u64* first, u32* pos,
                           u64* counter, hipStream_t s);

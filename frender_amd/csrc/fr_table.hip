@@ -44,20 +44,29 @@ hipError_t launch_table_init(GSlot* slots, u64 n, DevState* st, hipStream_t s) {
     return hipGetLastError();
 }
 
-// re-insert overflow entries (after the table has grown); presence is re-derived
-__global__ void reinsert_kernel(Table t, DevState* st, const Overflow* src, u64 n) {
+__device__ __forceinline__ bool last_block(u32* ctr);
+
+// re-insert overflow entries (after the table has grown); presence is re-derived.  An entry whose probe
+// window is still full goes on the (fresh) overflow list again: the grid's last workgroup reports how many did,
+// straight into pinned host memory, and grow_table grows the table until none is left.  The counter is the
+// aggregation's (zero between launches, and zero again afterwards).
+__global__ void reinsert_kernel(Table t, DevState* st, const Overflow* src, u64 n, u64* left_out) {
     u32 made = 0;
     for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
         const Overflow o = src[i];
         made += global_insert(t, st, o.key, o.count, o.first, o.tag) ? 1u : 0u;
     }
     add_created(st, made);
+    if (last_block(&st->log_red_done) && threadIdx.x == 0) {
+        *left_out = __hip_atomic_load(&st->n_overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence_system();
+    }
 }
 
-hipError_t launch_reinsert_overflow(Table t, DevState* st, const Overflow* src, u64 n, hipStream_t s) {
+hipError_t launch_reinsert_overflow(Table t, DevState* st, const Overflow* src, u64 n, u64* left_out, hipStream_t s) {
     if (!n) return hipSuccess;
     const int grid = (int)std::min<u64>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(reinsert_kernel, dim3(grid), dim3(256), 0, s, t, st, src, n);
+    hipLaunchKernelGGL(reinsert_kernel, dim3(grid), dim3(256), 0, s, t, st, src, n, left_out);
     return hipGetLastError();
 }
 
